@@ -17,7 +17,13 @@ Philox element offset), so the N-GPU images are the 1-GPU images of batch N*B bi
 scaling, no data-path collective); the only collectives are the timing barriers and the
 max-over-ranks reduction of the elapsed time (and the image gather of --save-images, after timing).
 
-Also reports, on one JSON line:
+A plain run sets up, warms up, times the `--steps` passes, writes `--dump-outputs` if asked and prints
+one JSON line with the headline figure (`value`, `ms_per_step`).  `--dump-outputs DIR` writes the images
+the last timed pass returned to DIR/images.npy (float32; all ranks' images in rank order, written by
+rank 0; a fixed seeded sample of whole images when they exceed 64 MB).  Seeds, weights and conditioning
+are fixed, so two runs with the same arguments sample from identical inputs.
+
+`--full` adds, on the same JSON line, from runs of their own after the timed region:
   roofline     — the split-path conv kernels (k_conv3lg / k_conv3g / k_conv4s2g / k_lin1x1), timed with
                  HIP events around every conv launch on its own stream in a SEPARATE one-lane pass of the
                  same K sampling passes after the timed region (`one_lane`; with 4 lanes' kernels co-running
@@ -51,6 +57,7 @@ FWD_PER_IMG = 602                # 300 steps x 2 CFG evaluations + 2 for the fin
 FP32_PEAK_TFLOPS = 157.3         # MI355X fp32 MFMA (= vector) peak, MI355X_MICROARCH.md
 F16_PEAK_TFLOPS = 2500.0         # MI355X dense f16/bf16 MFMA peak (no sparsity), MI355X_MICROARCH.md
 SPLIT_PRODUCTS = 3               # f16x3: hi*hi + hi*lo + lo*hi MFMAs per fp32 multiply-add
+DUMP_MAX_BYTES = 64 * 10**6      # --dump-outputs writes at most this much
 # HBM bytes per conv launch (the launches the roofline times), measured by rocprofv3 PMC passes on
 # this sampler in the roofline's own configuration (one lane: Bt = 256 rows per launch, as the timed
 # one-lane pass; tools/gpu/r06finb.sh -> tools/pmc_traffic.py, profiles/r06_fin_pmc_traffic.txt):
@@ -153,7 +160,14 @@ def main() -> int:
     ap.add_argument("--base-ch", type=int, default=96)
     ap.add_argument("--img-size", type=int, default=64,
                     help="64 (the metric's config 2); 256 with --batch 64 = config 5's per-GPU share (512 over 8)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the one-lane roofline pass (`roofline`, `one_lane`), the "
+                         "fp32-MFMA path (`fp32_path`) and the CPU baseline (`cpu_baseline`); a plain run reports the "
+                         "headline figure only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed passes write the images the last one returned (all ranks', in rank order, "
+                         "from rank 0) to DIR/images.npy in float32; above 64 MB a fixed seeded sample of whole images")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
     ap.add_argument("--cpu-batch", type=int, default=128)
     ap.add_argument("--lanes", "--lanes-alt", dest="lanes", type=int, default=4,
                     help="concurrent sampling lanes of the timed region (tcx_set_sample_lanes, 1-4; images are "
@@ -161,7 +175,7 @@ def main() -> int:
     ap.add_argument("--precision", choices=["f16x3", "fp32", "bf16"], default="f16x3",
                     help="conv arithmetic: f16x3 split MFMA (fp32-grade, default) or fp32 MFMA")
     ap.add_argument("--fp32-passes", type=int, default=1,
-                    help="with the f16x3 headline: timed one-lane passes of the fp32-MFMA path reported beside it "
+                    help="with --full and the f16x3 headline: timed one-lane passes of the fp32-MFMA path reported beside it "
                          "(`fp32_path`; 0 skips)")
     ap.add_argument("--cpu-steps-a", type=int, default=2)
     ap.add_argument("--cpu-steps-b", type=int, default=4)
@@ -246,69 +260,10 @@ def main() -> int:
     if used_conv_precision() != args.precision:
         raise SystemExit(f"bench: requested {args.precision} but the sampler ran in {used_conv_precision()}")
 
-    # Roofline pass: the same K passes on ONE stream with the conv launches bracketed by HIP events
-    # (with kernels of several streams co-running, a per-launch event duration no longer times a
-    # kernel alone).  Not part of `value`.
-    L.tcx_set_sample_lanes(1)
-    run(-100)
-    torch.cuda.synchronize(device)
-    L.tcx_prof_enable(1)
-    el1 = timed(lambda i: run(100 + i))
-    ms, n, fl = ctypes.c_double(), ctypes.c_longlong(), ctypes.c_double()
-    L.tcx_prof_read(ctypes.byref(ms), ctypes.byref(n), ctypes.byref(fl))
-    L.tcx_prof_enable(0)
-    L.tcx_set_sample_lanes(prev_lanes)
-    out = _last_out[0]
-    assert out is not None and bool(torch.isfinite(out).all()) and float(out.min()) >= 0.0 and float(out.max()) <= 1.0
-
-    # The fp32-MFMA path beside the f16x3 headline (same sampler, one lane, conv launches timed by
-    # HIP events as above): what the f16x3 split path buys at equal (fp32-grade) parity gates.
-    fp32_path = None
-    if args.precision == "f16x3" and args.fp32_passes > 0:
-        set_conv_precision("fp32")
-        L.tcx_set_sample_lanes(1)
-        run(-200)
-        torch.cuda.synchronize(device)
-        steps_saved = args.steps
-        args.steps = args.fp32_passes
-        L.tcx_prof_enable(1)
-        el32 = timed(lambda i: run(200 + i))
-        ms32, n32, fl32 = ctypes.c_double(), ctypes.c_longlong(), ctypes.c_double()
-        L.tcx_prof_read(ctypes.byref(ms32), ctypes.byref(n32), ctypes.byref(fl32))
-        L.tcx_prof_enable(0)
-        L.tcx_set_sample_lanes(prev_lanes)
-        set_conv_precision(args.precision)
-        ach32 = (fl32.value / max(1, n32.value)) / ((ms32.value / max(1, n32.value)) * 1e-3) / 1e12 if n32.value else 0.0
-        fp32_path = {"value": round(world * B * args.fp32_passes / el32, 4), "unit": "images/s", "lanes": 1,
-                     "passes": args.fp32_passes, "ms_per_step": round(el32 / args.fp32_passes * 1e3, 3),
-                     "roofline": {"bound": "mfma", "kernel": "k_conv (fp32-MFMA implicit GEMM, v_mfma_f32_32x32x2_f32)",
-                                  "achieved": round(ach32, 3), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                  "frac": round(ach32 / FP32_PEAK_TFLOPS, 4),
-                                  "avg_launch_ms": round(ms32.value / max(1, n32.value), 5)}}
-        args.steps = steps_saved
-
-    if args.precision == "f16x3":
-        kname = ("split-path convs: k_conv3m (3x3 at 16/32/64-px rows, v_mfma_f32_16x16x32_f16; h2 sources or the "
-                 "GroupNorm+SiLU prologue form), k_conv4s2g (4x4/s2, LDS-DMA), k_lin1x1 (1x1) — f16x3, 3 f16 "
-                 "MFMAs per fp32 MAC; all conv launches of the pass")
-        peak = F16_PEAK_TFLOPS / SPLIT_PRODUCTS
-        peak_basis = "2500 TFLOP/s dense f16 MFMA / 3 products per fp32 MAC; achieved in fp32-equivalent FLOPs"
-    elif args.precision == "bf16":
-        kname = ("bf16 single-product convs (config 5): k_conv3lb (LDS-DMA 3x3 at 64/128/256-px rows, "
-                 "v_mfma_f32_32x32x16_bf16; TCX_CONV3MB=1 adds k_conv3mb's 16x16x32 tap pairs at Cin >= 192), "
-                 "k_conv4s2g (chunk-major skip planes), k_lin1x1 — one bf16 MFMA per MAC; all conv launches of the pass")
-        peak = F16_PEAK_TFLOPS
-        peak_basis = "2500 TFLOP/s dense bf16 MFMA"
-    else:
-        kname = "k_conv (fp32-MFMA implicit-GEMM conv, v_mfma_f32_32x32x2_f32)"
-        peak = FP32_PEAK_TFLOPS
-        peak_basis = "157.3 TFLOP/s fp32 MFMA"
+    assert timed_out is not None and bool(torch.isfinite(timed_out).all()) \
+        and float(timed_out.min()) >= 0.0 and float(timed_out.max()) <= 1.0
     images = world * B * args.steps
     value = images / elapsed
-    conv_avg_ms = ms.value / max(1, n.value)
-    conv_avg_flop = fl.value / max(1, n.value)
-    achieved = conv_avg_flop / (conv_avg_ms * 1e-3) / 1e12 if n.value else 0.0
-    traffic = TRAFFIC_BYTES_PER_CONV_LAUNCH.get((args.precision, S))
     result = {
         "metric": "denoised images/sec (300-step reverse-SDE, CFG=1.5) at 1/2/4/8 MI355X",
         "value": round(value, 4),
@@ -329,24 +284,86 @@ def main() -> int:
                    "image": [1, S, S], "conv_precision": args.precision, "sample_lanes": max(1, args.lanes),
                    "parallelism": "replicas" if world == 1 else f"dp{world} (independent shards)"},
         "path_tflops": round(value / world * FWD_PER_IMG * GFLOP_PER_IMG_FWD / 1e3, 3) if S == 64 else None,
-        "roofline": {"bound": "mfma", "kernel": kname, "achieved": round(achieved, 3), "peak": round(peak, 1),
-                     "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
-                     "traffic": traffic,
-                     "traffic_unit": "HBM bytes per conv launch",
-                     "traffic_source": TRAFFIC_SOURCE[(args.precision, S)] if traffic is not None else
-                     "not measured for this configuration (PMC passes exist for the 64x64 f16x3 headline and the "
-                     "256x256 bf16 config 5 only)",
-                     "peak_basis": peak_basis,
-                     "measured_on": "one-lane roofline pass (same K sampling passes on one stream, HIP events per conv launch)",
-                     "avg_launch_ms": round(conv_avg_ms, 5), "avg_launch_gflop": round(conv_avg_flop / 1e9, 4),
-                     "launches": n.value,
-                     "conv_share_of_step": round(ms.value / 1e3 / el1, 4)},
-        "one_lane": {"value": round(images / el1, 4), "unit": "images/s", "ms_per_step": round(el1 / args.steps * 1e3, 3),
-                     "lanes_speedup": round(el1 / elapsed, 4)},
     }
-    if fp32_path is not None:
-        result["fp32_path"] = fp32_path
-    if args.save_images:
+    if args.full:
+        # Roofline pass: the same K passes on ONE stream with the conv launches bracketed by HIP events
+        # (with kernels of several streams co-running, a per-launch event duration no longer times a
+        # kernel alone).  Not part of `value`.
+        L.tcx_set_sample_lanes(1)
+        run(-100)
+        torch.cuda.synchronize(device)
+        L.tcx_prof_enable(1)
+        el1 = timed(lambda i: run(100 + i))
+        ms, n, fl = ctypes.c_double(), ctypes.c_longlong(), ctypes.c_double()
+        L.tcx_prof_read(ctypes.byref(ms), ctypes.byref(n), ctypes.byref(fl))
+        L.tcx_prof_enable(0)
+        L.tcx_set_sample_lanes(prev_lanes)
+
+        # The fp32-MFMA path beside the f16x3 headline (same sampler, one lane, conv launches timed by
+        # HIP events as above): what the f16x3 split path buys at equal (fp32-grade) parity gates.
+        fp32_path = None
+        if args.precision == "f16x3" and args.fp32_passes > 0:
+            set_conv_precision("fp32")
+            L.tcx_set_sample_lanes(1)
+            run(-200)
+            torch.cuda.synchronize(device)
+            steps_saved = args.steps
+            args.steps = args.fp32_passes
+            L.tcx_prof_enable(1)
+            el32 = timed(lambda i: run(200 + i))
+            ms32, n32, fl32 = ctypes.c_double(), ctypes.c_longlong(), ctypes.c_double()
+            L.tcx_prof_read(ctypes.byref(ms32), ctypes.byref(n32), ctypes.byref(fl32))
+            L.tcx_prof_enable(0)
+            L.tcx_set_sample_lanes(prev_lanes)
+            set_conv_precision(args.precision)
+            ach32 = (fl32.value / max(1, n32.value)) / ((ms32.value / max(1, n32.value)) * 1e-3) / 1e12 if n32.value else 0.0
+            fp32_path = {"value": round(world * B * args.fp32_passes / el32, 4), "unit": "images/s", "lanes": 1,
+                         "passes": args.fp32_passes, "ms_per_step": round(el32 / args.fp32_passes * 1e3, 3),
+                         "roofline": {"bound": "mfma", "kernel": "k_conv (fp32-MFMA implicit GEMM, v_mfma_f32_32x32x2_f32)",
+                                      "achieved": round(ach32, 3), "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                      "frac": round(ach32 / FP32_PEAK_TFLOPS, 4),
+                                      "avg_launch_ms": round(ms32.value / max(1, n32.value), 5)}}
+            args.steps = steps_saved
+
+        if args.precision == "f16x3":
+            kname = ("split-path convs: k_conv3m (3x3 at 16/32/64-px rows, v_mfma_f32_16x16x32_f16; h2 sources or the "
+                     "GroupNorm+SiLU prologue form), k_conv4s2g (4x4/s2, LDS-DMA), k_lin1x1 (1x1) — f16x3, 3 f16 "
+                     "MFMAs per fp32 MAC; all conv launches of the pass")
+            peak = F16_PEAK_TFLOPS / SPLIT_PRODUCTS
+            peak_basis = "2500 TFLOP/s dense f16 MFMA / 3 products per fp32 MAC; achieved in fp32-equivalent FLOPs"
+        elif args.precision == "bf16":
+            kname = ("bf16 single-product convs (config 5): k_conv3lb (LDS-DMA 3x3 at 64/128/256-px rows, "
+                     "v_mfma_f32_32x32x16_bf16; TCX_CONV3MB=1 adds k_conv3mb's 16x16x32 tap pairs at Cin >= 192), "
+                     "k_conv4s2g (chunk-major skip planes), k_lin1x1 — one bf16 MFMA per MAC; all conv launches of the pass")
+            peak = F16_PEAK_TFLOPS
+            peak_basis = "2500 TFLOP/s dense bf16 MFMA"
+        else:
+            kname = "k_conv (fp32-MFMA implicit-GEMM conv, v_mfma_f32_32x32x2_f32)"
+            peak = FP32_PEAK_TFLOPS
+            peak_basis = "157.3 TFLOP/s fp32 MFMA"
+        conv_avg_ms = ms.value / max(1, n.value)
+        conv_avg_flop = fl.value / max(1, n.value)
+        achieved = conv_avg_flop / (conv_avg_ms * 1e-3) / 1e12 if n.value else 0.0
+        traffic = TRAFFIC_BYTES_PER_CONV_LAUNCH.get((args.precision, S))
+        result.update({
+            "roofline": {"bound": "mfma", "kernel": kname, "achieved": round(achieved, 3), "peak": round(peak, 1),
+                         "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
+                         "traffic": traffic,
+                         "traffic_unit": "HBM bytes per conv launch",
+                         "traffic_source": TRAFFIC_SOURCE[(args.precision, S)] if traffic is not None else
+                         "not measured for this configuration (PMC passes exist for the 64x64 f16x3 headline and the "
+                         "256x256 bf16 config 5 only)",
+                         "peak_basis": peak_basis,
+                         "measured_on": "one-lane roofline pass (same K sampling passes on one stream, HIP events per conv launch)",
+                         "avg_launch_ms": round(conv_avg_ms, 5), "avg_launch_gflop": round(conv_avg_flop / 1e9, 4),
+                         "launches": n.value,
+                         "conv_share_of_step": round(ms.value / 1e3 / el1, 4)},
+            "one_lane": {"value": round(images / el1, 4), "unit": "images/s", "ms_per_step": round(el1 / args.steps * 1e3, 3),
+                         "lanes_speedup": round(el1 / elapsed, 4)},
+        })
+        if fp32_path is not None:
+            result["fp32_path"] = fp32_path
+    if args.save_images or args.dump_outputs:
         imgs = timed_out
         if world > 1:
             from toycrystals_amd.dist import all_gather_
@@ -355,8 +372,17 @@ def main() -> int:
             imgs = torch.cat(bufs, 0)
         if rank == 0:
             import numpy as np
-            np.save(args.save_images, imgs.cpu().numpy())
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            imgs = imgs.cpu().numpy()
+            if args.save_images:
+                np.save(args.save_images, imgs)
+            if args.dump_outputs:
+                imgs = np.ascontiguousarray(imgs, dtype=np.float32)
+                keep = DUMP_MAX_BYTES // (imgs[0].nbytes)
+                if keep < imgs.shape[0]:  # whole images at fixed, seeded indices (ascending)
+                    imgs = imgs[np.sort(np.random.default_rng(0).choice(imgs.shape[0], size=keep, replace=False))]
+                os.makedirs(args.dump_outputs, exist_ok=True)
+                np.save(os.path.join(args.dump_outputs, "images.npy"), imgs)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(model.state_dict(), args.cpu_batch, args.cpu_steps_a, args.cpu_steps_b,
                                               args.cfg, args.t_end)
     if rank == 0:
