@@ -233,6 +233,18 @@ int tcx_attention_h2(const float* qkv, void* out, int Bt, int N, int C, int head
  * (attention_split.hip): N % 256 == 0, head dim 16, 32, 48 or 64.  Replaces the SDPA of
  * SelfAttention2d (sde_score_model.py:150-160) in the split-precision evaluator. */
 int tcx_attention_split(const void* qkv, void* out, int Bt, int N, int C, int heads, void* stream);
+/* The whole attention block of SelfAttention2d (sde_score_model.py:136-167) of the split-precision
+ * evaluator's bottleneck, N = 256 tokens, C = 192, 4 heads: a = a + proj(attention(qkv(xh))) in place on
+ * the fp32 residual a [Bt,N,C].  xh: h2 records of attn.norm(a); qkv_* / proj_*: the 1x1 convs' packed h2
+ * weights (tcx_pack_conv_weight_h2), *wscale and biases; oh: [Bt,N,C] h2 scratch (the attention output,
+ * distinct from xh and a).  The qkv conv runs inside the attention workgroup (csrc/attn_block.hip), so the
+ * qkv tensor never reaches memory; proj + residual is the 1x1 GEMM launch of tcx_conv2d_h2.  Same products
+ * in the same order as tcx_conv2d_h2 + tcx_attention_split + tcx_conv2d_h2: bit-identical.  ovf is raised
+ * when a q, k or v value leaves the f16 range. */
+int tcx_attn_block_h2(const void* xh, float* a, void* oh, const void* qkv_wh, const float* qkv_wscale,
+                      const float* qkv_b, int qkv_cout_pad, const void* proj_wh, const float* proj_wscale,
+                      const float* proj_b, int proj_cout_pad, int Bt, int N, int C, int heads, unsigned* ovf,
+                      void* stream);
 /* Conversions of n elements (n % 8 == 0, channel-fastest tensors with C % 8 == 0). */
 int tcx_f32_to_h2(const float* x, void* y, size_t n, unsigned* ovf, void* stream);
 int tcx_h2_to_f32(const void* x, float* y, size_t n, void* stream);

@@ -73,6 +73,9 @@ LAYERS = [
 # round 5: k_attn_prep replaces positions 18-21 (apply GN5, attn.norm statistics, finalize, apply)
 ATTN4 = slice(18, 22)
 ATTN_PREP = ("mid GN+SiLU + attn.norm stats/tables + records", mem(3 * BT * P2 * C2 * E4))
+# k_attn_block replaces the qkv 1x1 launch and the attention launch (their FLOPs in one row)
+ATTN_BLOCK = ("attn qkv 1x1 + attention (4 heads, d 48, N 256)",
+              ("mfma", 2.0 * BT * P2 * C2 * 3 * C2 + 2.0 * 2 * BT * 4 * P2 * P2 * (C2 // 4)))
 
 
 def main() -> int:
@@ -84,6 +87,9 @@ def main() -> int:
     global LAYERS
     if any(r[1].startswith("k_attn_prep") for r in rows):
         LAYERS = LAYERS[:ATTN4.start] + [ATTN_PREP] + LAYERS[ATTN4.stop:]
+    if any(r[1].startswith("k_attn_block") for r in rows):
+        i = [l[0] for l in LAYERS].index("attn qkv 1x1")
+        LAYERS = LAYERS[:i] + [ATTN_BLOCK] + LAYERS[i + 2:]
     if len(rows) != len(LAYERS):
         print(f"expected {len(LAYERS)} kernels per evaluation, got {len(rows)}", file=sys.stderr)
         return 1

@@ -36,6 +36,9 @@ int gn_apply_b2cm(const void* x, void* y, int Bt, int HW, int C, const float* sc
 int gn_apply_cm(const float* x, void* y, int Bt, int HW, int C, const float* scale, const float* shift,
                 unsigned* ovf, hipStream_t st);
 int attention_split(const void* qkv, void* out, int Bt, int N, int C, int heads, int bf, hipStream_t st);
+// attn_block.hip: the qkv conv inside the attention workgroup (f16x3, N = 256, C = 192, 4 heads)
+bool attn_block_ok(int fmt, int Bt, int N, int C, int heads, const tcx_conv& qkv, const tcx_conv& proj, const void* x,
+                   const void* a, const void* o);
 }
 
 #include <cmath>
@@ -1114,6 +1117,16 @@ bool attn_split_enabled() {
     return on;
 }
 
+// TCX_ATTN_BLOCK=0: the bottleneck attention as three launches (qkv conv, k_attention_split, proj conv)
+// instead of k_attn_block + proj (bit-identical; A/B measurements and parity tests)
+bool attn_block_enabled() {
+    static const bool on = [] {
+        const char* e = getenv("TCX_ATTN_BLOCK");
+        return !(e && e[0] == '0');
+    }();
+    return on;
+}
+
 int groups_of(int ch) {
     for (int g : {8, 4, 2})
         if (ch % g == 0) return g;
@@ -1360,15 +1373,25 @@ int unet_body(const tcx_unet* net, const Plan& P, const float* x, int B, const f
         const int D = C2 / net->heads;
         const bool split_attn = h2.on && attn_split_enabled() && P.P2 % 256 == 0 && C2 % net->heads == 0 &&
                                 (D == 16 || D == 32 || D == 48 || D == 64);
-        TCX_TRY(conv_gn(q, P.b16, nullptr, C2, 0, Bt, 0, H2, W2, 1, 0, nullptr, nullptr, P.qkv, nullptr, &dummy, st,
-                        nullptr, nullptr, nullptr, nullptr, h2, split_attn ? 1 : 0));
-        TCX_REQUIRE(split_attn || !h2.bf, "tcx_unet: bf16 precision needs the split attention (N %% 256 == 0)");
-        if (split_attn) TCX_TRY(attention_split(P.qkv, P.b16, Bt, P.P2, C2, net->heads, fmt, st));
-        else if (h2.on) TCX_TRY(tcx_attention_h2(P.qkv, P.b16, Bt, P.P2, C2, net->heads, h2.ovf, st));
-        else TCX_TRY(tcx_attention(P.qkv, P.b16, Bt, P.P2, C2, net->heads, st));
-        const tcx_conv& pr = net->proj;
-        TCX_TRY(conv_gn(pr, P.b16, nullptr, C2, 0, Bt, 0, H2, W2, 1, 0, nullptr, P.a16, P.a16, nullptr, &dummy, st,
-                        nullptr, nullptr, nullptr, nullptr, h2));
+        // f16x3 at N = 256, C2 = 192, 4 heads: the qkv conv runs inside the attention workgroup
+        // (attn_block.hip; its output goes to the free qkv buffer, since the heads of an image read b16
+        // while others already write), then the proj launch as below
+        if (h2.on && split_attn && attn_block_enabled() &&
+            attn_block_ok(fmt, Bt, P.P2, C2, net->heads, q, net->proj, P.b16, P.a16, P.qkv)) {
+            const tcx_conv& pr = net->proj;
+            TCX_TRY(tcx_attn_block_h2(P.b16, P.a16, P.qkv, q.wh, q.wscale, q.b, q.cout_pad, pr.wh, pr.wscale, pr.b,
+                                      pr.cout_pad, Bt, P.P2, C2, net->heads, h2.ovf, st));
+        } else {
+            TCX_TRY(conv_gn(q, P.b16, nullptr, C2, 0, Bt, 0, H2, W2, 1, 0, nullptr, nullptr, P.qkv, nullptr, &dummy, st,
+                            nullptr, nullptr, nullptr, nullptr, h2, split_attn ? 1 : 0));
+            TCX_REQUIRE(split_attn || !h2.bf, "tcx_unet: bf16 precision needs the split attention (N %% 256 == 0)");
+            if (split_attn) TCX_TRY(attention_split(P.qkv, P.b16, Bt, P.P2, C2, net->heads, fmt, st));
+            else if (h2.on) TCX_TRY(tcx_attention_h2(P.qkv, P.b16, Bt, P.P2, C2, net->heads, h2.ovf, st));
+            else TCX_TRY(tcx_attention(P.qkv, P.b16, Bt, P.P2, C2, net->heads, st));
+            const tcx_conv& pr = net->proj;
+            TCX_TRY(conv_gn(pr, P.b16, nullptr, C2, 0, Bt, 0, H2, W2, 1, 0, nullptr, P.a16, P.a16, nullptr, &dummy, st,
+                            nullptr, nullptr, nullptr, nullptr, h2));
+        }
     }
     // us2: bilinear x2 (edge-clamped) into the free b32 buffer, then the circular 3x3 conv -> a32.
     // (The upsample-on-load conv variant re-reads 4 source taps per im2col element and measured
