@@ -558,7 +558,7 @@ int tcx_gn_stats(const double* part, int Bt, int HW, int C, int groups, int nspl
                  void* stream);
 
 /* Backward of y = silu?(GroupNorm(x)) (silu = 1: the _ConvBlock GN+SiLU pair, :103-105; 0: the
- * attention norm, :150).  dgamma/dbeta optional. */
+ * attention norm, :150).  dgamma/dbeta optional.  C % 4 == 0 and 0 < C <= 1024. */
 size_t tcx_gn_bwd_workspace(int Bt, int HW, int C);
 int tcx_gn_bwd(const float* x, const float* dy, const float* scale, const float* shift, const float* mean,
                const float* rstd, const float* gamma, int Bt, int HW, int C, int groups, int silu, float* dx,

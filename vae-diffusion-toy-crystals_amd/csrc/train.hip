@@ -505,8 +505,11 @@ __global__ void k_embedding_bwd(const int64_t* __restrict__ idx, const float* __
 }
 
 // ---------------------------------------------------------------- LayerNorm (+FiLM)
-// y = l*(1+gm) + bt with l = (x*rstd - mean*rstd)*w + b (ATen's CPU LayerNorm form), gm/bt the
+// y = l*(1+gm) + bt with l = ((x - mean)*rstd)*w + b, gm/bt the
 // two halves of a FiLM row gb[r][0:Wd | Wd:2Wd] (null: plain LayerNorm).  One block per row.
+// (x - mean) is formed first, as k_ln_bwd forms xhat: x*rstd - mean*rstd rounds mean*rstd at its own
+// size, an absolute error of 2^-24 |mean| rstd in xhat that a row of small variance (rstd up to
+// 1/sqrt(eps)) around a large mean turns into 1e-4 and more of y.
 __global__ __launch_bounds__(256) void k_ln_fwd(const float* __restrict__ x, float* __restrict__ y, int Wd,
                                                 const float* __restrict__ w, const float* __restrict__ bb,
                                                 const float* __restrict__ gb, int ld_gb, float eps,
@@ -539,12 +542,17 @@ __global__ __launch_bounds__(256) void k_ln_fwd(const float* __restrict__ x, flo
         mean[r] = muf;
         rstd[r] = rs;
     }
-    const float sft = -muf * rs;
     for (int c = threadIdx.x; c < Wd; c += 256) {
-        float l = fmaf(xr[c], rs, sft) * w[c] + bb[c];
+        float l = ((xr[c] - muf) * rs) * w[c] + bb[c];
         if (gb) l = l * (1.0f + gb[(size_t)r * ld_gb + c]) + gb[(size_t)r * ld_gb + Wd + c];
         y[(size_t)r * Wd + c] = l;
     }
+}
+
+// a * b rounded to float, never fused into a following add or subtract
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
 }
 
 // Backward of k_ln_fwd: dx, and per-row products for the column reductions: dwrow = dl*xhat,
@@ -565,14 +573,16 @@ __global__ __launch_bounds__(256) void k_ln_bwd(const float* __restrict__ x, con
         const float xh = (xr[c] - mu) * rs;
         float dl = gr[c];
         if (gb) {
-            const float l = xh * w[c] + bb[c];
-            dgb[(size_t)r * 2 * Wd + c] = dl * l;
+            // l = xhat*w + b in fp64 from the fp32 inputs: the two terms cancel where l is near 0, and an
+            // fp32 xhat would leave 2^-24 |xhat*w| there, far above the size of dh*l itself
+            const double l = ((double)xr[c] - (double)mu) * (double)rs * (double)w[c] + (double)bb[c];
+            dgb[(size_t)r * 2 * Wd + c] = (float)((double)dl * l);
             dgb[(size_t)r * 2 * Wd + Wd + c] = dl;
             dl = dl * (1.0f + gb[(size_t)r * ld_gb + c]);
         }
         dwrow[(size_t)r * Wd + c] = dl * xh;
         dbrow[(size_t)r * Wd + c] = dl;
-        const float dxh = dl * w[c];
+        const float dxh = mul_rounded(dl, w[c]);
         s1 += dxh;
         s2 += (double)dxh * xh;
     }
@@ -591,7 +601,9 @@ __global__ __launch_bounds__(256) void k_ln_bwd(const float* __restrict__ x, con
         const float xh = (xr[c] - mu) * rs;
         float dl = gr[c];
         if (gb) dl = dl * (1.0f + gb[(size_t)r * ld_gb + c]);
-        const float dxh = dl * w[c];
+        // the rounded product, as summed into m1 above: fused into dxh - m1 the unrounded one leaves its
+        // rounding residual times rstd in dx (Wd = 1: exact dx 0, rstd = 1/sqrt(eps))
+        const float dxh = mul_rounded(dl, w[c]);
         dx[(size_t)r * Wd + c] = rs * (dxh - m1 - xh * m2);
     }
 }
@@ -949,6 +961,8 @@ extern "C" int tcx_gn_bwd_absmax(const float* x, const float* dy, const float* s
                                  int groups, int silu, float* dx, float* dgamma, float* dbeta, unsigned* amax, void* ws,
                                  size_t ws_bytes, void* stream) {
     TCX_REQUIRE(x && dy && scale && shift && mean && rstd && dx && ws, "tcx_gn_bwd: null pointer");
+    // k_gn_bwd_partials covers the channel quads tid < 256 only: C / 4 <= 256 (and lanes = 256 / (C / 4) needs C > 0)
+    TCX_REQUIRE(C > 0 && C <= 1024, "tcx_gn_bwd: need 0 < C <= 1024 (one 256-thread block spans the C / 4 channel quads)");
     TCX_REQUIRE(C % 4 == 0 && groups > 0 && C % groups == 0 && Bt >= 0 && HW > 0, "tcx_gn_bwd: need C %% 4 == 0");
     TCX_REQUIRE(ws_bytes >= tcx_gn_bwd_workspace(Bt, HW, C), "tcx_gn_bwd: workspace too small");
     TCX_REQUIRE(aligned16(x) && aligned16(dy) && aligned16(dx) && aligned16(scale) && aligned16(shift),
