@@ -991,6 +991,13 @@ extern "C" int tcx_conv_wgrad(const float* x1, const float* x2, int Bt, int H, i
     TCX_REQUIRE(x1 && dy && dw && ws, "tcx_conv_wgrad: null pointer");
     TCX_REQUIRE((C2 == 0) == (x2 == nullptr) && C1 > 0 && C2 >= 0 && Cout > 0 && Bt >= 0, "tcx_conv_wgrad: bad shape");
     TCX_REQUIRE(ks >= 1 && stride >= 1 && pad >= 0, "tcx_conv_wgrad: bad geometry");
+    // C division truncates a negative numerator to 0 (Ho = 1 for H + 2 pad < ks at stride >= 2), and
+    // wrap_idx wraps once: circular indices stay in range only for pad <= H, W.  torch refuses both.
+    TCX_REQUIRE(H > 0 && W > 0, "tcx_conv_wgrad: empty input (H = %d, W = %d)", H, W);
+    TCX_REQUIRE(H + 2 * pad >= ks && W + 2 * pad >= ks, "tcx_conv_wgrad: kernel %d larger than the padded input %d x %d",
+                ks, H + 2 * pad, W + 2 * pad);
+    TCX_REQUIRE(!circular || (pad <= H && pad <= W), "tcx_conv_wgrad: circular pad %d wraps more than once (input %d x %d)",
+                pad, H, W);
     WgParams p{};
     p.x1 = x1; p.x2 = x2; p.C1 = C1; p.C2 = C2; p.Cin = C1 + C2; p.H = H; p.W = W;
     p.Ho = (H + 2 * pad - ks) / stride + 1;
@@ -1012,7 +1019,9 @@ extern "C" int tcx_conv_wgrad(const float* x1, const float* x2, int Bt, int H, i
         const size_t plane = (size_t)p.K * Cout * sizeof(float);
         const size_t room = (ws_bytes - (size_t)(base - (char*)ws)) / plane;
         const int ns = thin_wgrad_plan(Bt, H, W, C1, Cout, ks, stride, (int)std::min<size_t>(room, 256), &a);
-        if (ns > 0 && p.Ho == H && p.Wo == W) {
+        // W = 1 circular stays on k_wgrad: k_thin_wgrad's look-ahead tv(x0 + i + 2) wraps once, wrap_idx(2, 1) = 1,
+        // and reads one float past the thin operand's last row (the value is never used)
+        if (ns > 0 && p.Ho == H && p.Wo == W && !(circular && W < 2)) {
             const bool cout1 = Cout == 1;
             a.wide = cout1 ? x1 : dy;
             a.thin = cout1 ? dy : x1;
@@ -1054,6 +1063,13 @@ extern "C" int tcx_conv_wgrad_h2(const void* x1, const void* x2, int Bt, int H, 
     TCX_REQUIRE((C2 == 0) == (x2 == nullptr) && C1 > 0 && C1 % 8 == 0 && C2 % 8 == 0 && Cout % 8 == 0 && Bt >= 0,
                 "tcx_conv_wgrad_h2: needs C1, C2, Cout %% 8 == 0 (h2 records)");
     TCX_REQUIRE(ks >= 1 && stride >= 1 && pad >= 0, "tcx_conv_wgrad_h2: bad geometry");
+    // C division truncates a negative numerator to 0 (Ho = 1 for H + 2 pad < ks at stride >= 2), and
+    // wrap_idx wraps once: circular indices stay in range only for pad <= H, W.  torch refuses both.
+    TCX_REQUIRE(H > 0 && W > 0, "tcx_conv_wgrad_h2: empty input (H = %d, W = %d)", H, W);
+    TCX_REQUIRE(H + 2 * pad >= ks && W + 2 * pad >= ks, "tcx_conv_wgrad_h2: kernel %d larger than the padded input %d x %d",
+                ks, H + 2 * pad, W + 2 * pad);
+    TCX_REQUIRE(!circular || (pad <= H && pad <= W), "tcx_conv_wgrad_h2: circular pad %d wraps more than once (input %d x %d)",
+                pad, H, W);
     TCX_REQUIRE(aligned16(x1) && (!x2 || aligned16(x2)) && aligned16(dy), "tcx_conv_wgrad_h2: 16-B alignment");
     WgParams p{};
     p.x1 = (const float*)x1; p.x2 = (const float*)x2; p.C1 = C1; p.C2 = C2; p.Cin = C1 + C2; p.H = H; p.W = W;
