@@ -68,7 +68,14 @@ int tcx_debug_conv_stamps(void* buf, int n);
  *     x -> silu(x * scale[b][c] + shift[b][c]) (tables [Bt][C] from tcx_gn_finalize), applied
  *     once per element as the staged tile is written to LDS — the normalised tensor never
  *     exists in HBM (sde_score_model.py:103-107 feeding the next conv).  Needs Cin, C1 % 32 == 0,
- *     circular padding, Ho*Wo % 128 == 0.  */
+ *     circular padding, Ho*Wo % 128 == 0.
+ * Refused with TCX_EINVAL before any launch, as torch refuses them (Hi, Wi = the input after the
+ * optional upsample): a kernel larger than the padded input, Hi + 2 pad < ks or Wi + 2 pad < ks
+ * (Ho = floor((Hi + 2 pad - ks) / stride) + 1 is only defined from there on); circular padding with
+ * pad > Hi or pad > Wi (the halo wraps once); upsample with zero padding, Cin % 4 != 0 or a source
+ * not 16-B aligned.  A source with C % 4 != 0 or a base not 16-B aligned takes scalar loads and must
+ * be the only source.  Stride-1 one-source convs with Cin = 1 or Cout = 1 run on the VALU kernels
+ * of thin.hip when their LDS staging fits 48 KB, and on the implicit GEMM otherwise.  */
 int tcx_conv2d(const float* x1, const float* x2, int Bt, int bmod, int H, int W, int C1, int C2,
                const float* wpk, const float* bias, const float* bias_b, const float* resid,
                float* y, int Cout, int cout_pad, int kpad, int ks, int stride, int pad,
@@ -200,7 +207,8 @@ int tcx_attention_split_b2(const void* qkv, void* out, int Bt, int N, int C, int
  * + 32: source 2 is chunk-major (3x3 shapes of k_conv3m); f16x3 records without prologue only, else
  * TCX_EINVAL.  With bf16 = 2 (config 5, round 6) the chunk-major planes are 2-byte bf16
  * ([C/8][bsrc*H*W][16 B], tcx_gn_apply_tab_b2_cm): + 16 on k_conv4s2g's slim 4x4/s2 shapes, + 32 on
- * k_conv3lb's 3x3 shapes (rows of 64 / 128 / 256 px). */
+ * k_conv3lb's 3x3 shapes (rows of 64 / 128 / 256 px).  Like tcx_conv2d, a kernel larger than the
+ * padded input and a circular pad > H or W are TCX_EINVAL. */
 int tcx_conv2d_h2_pro(const void* x1, const void* x2, int Bt, int bmod, int H, int W, int C1, int C2,
                       const void* wh, const void* wfrag, const float* wscale, const float* bias,
                       const float* bias_b,
@@ -543,7 +551,8 @@ int tcx_pack_conv_dgrad_weight(const float* w, float* wpk, int Cout, int Cin, in
 /* ConvTranspose2d(4, 2, 1) with circular (1) or zero (0) padding of the input grid: the data
  * gradient of the stride-2 circular downsample convs (ds1/ds2, sde_score_model.py:208,210; the
  * weight [Cout][Cin][4][4] packed by tcx_pack_convT_weight(w, wpk, Cout, Cin, ...)) and of the
- * VAE encoder convs (zero padding). */
+ * VAE encoder convs (zero padding).  Bt < 0, H, W, Cin or Cout <= 0 and act outside 0 .. 3 are
+ * TCX_EINVAL (tcx_convT2x likewise); Bt = 0 is TCX_OK and touches nothing. */
 int tcx_conv_transpose2x(const float* x, int Bt, int H, int W, int Cin, const float* wpk4, const float* bias,
                          float* y, int Cout, int cout_pad, int kpad, int act, int circular, void* stream);
 

@@ -619,6 +619,12 @@ extern "C" int tcx_conv2d_h2_pro(const void* x1, const void* x2, int Bt, int bmo
     ConvParams p{};
     p.x1 = (const float*)x1; p.x2 = (const float*)x2; p.C1 = C1; p.C2 = C2; p.Cin = Cin;
     p.bmod = bmod; p.H = H; p.W = W; p.Hi = H; p.Wi = W;
+    // C division truncates a negative numerator to 0 (Ho = 1 for H + 2 pad < ks at stride >= 2), and
+    // wrap_idx wraps once: circular indices stay in range only for pad <= H, W.  torch refuses both.
+    TCX_REQUIRE(H + 2 * pad >= ks && W + 2 * pad >= ks, "tcx_conv2d_h2: kernel %d larger than the padded input %d x %d",
+                ks, H + 2 * pad, W + 2 * pad);
+    TCX_REQUIRE(!circular || (pad <= H && pad <= W), "tcx_conv2d_h2: circular pad %d wraps more than once (input %d x %d)",
+                pad, H, W);
     p.Ho = (H + 2 * pad - ks) / stride + 1;
     p.Wo = (W + 2 * pad - ks) / stride + 1;
     TCX_REQUIRE(p.Ho > 0 && p.Wo > 0, "tcx_conv2d_h2: empty output");
@@ -732,6 +738,12 @@ extern "C" int tcx_conv2d(const float* x1, const float* x2, int Bt, int bmod, in
     p.bmod = bmod; p.H = H; p.W = W;
     p.Hi = upsample ? 2 * H : H;
     p.Wi = upsample ? 2 * W : W;
+    // C division truncates a negative numerator to 0 (Ho = 1 for Hi + 2 pad < ks at stride >= 2), and
+    // wrap_idx wraps once: circular indices stay in range only for pad <= Hi, Wi.  torch refuses both.
+    TCX_REQUIRE(p.Hi + 2 * pad >= ks && p.Wi + 2 * pad >= ks, "tcx_conv2d: kernel %d larger than the padded input %d x %d",
+                ks, p.Hi + 2 * pad, p.Wi + 2 * pad);
+    TCX_REQUIRE(!circular || (pad <= p.Hi && pad <= p.Wi), "tcx_conv2d: circular pad %d wraps more than once (input %d x %d)",
+                pad, p.Hi, p.Wi);
     p.Ho = (p.Hi + 2 * pad - ks) / stride + 1;
     p.Wo = (p.Wi + 2 * pad - ks) / stride + 1;
     TCX_REQUIRE(p.Ho > 0 && p.Wo > 0, "tcx_conv2d: empty output");
@@ -792,6 +804,8 @@ extern "C" int tcx_conv_transpose2x(const float* x, int Bt, int H, int W, int Ci
                                     const float* bias, float* y, int Cout, int cout_pad, int kpad, int act,
                                     int circular, void* stream) {
     TCX_REQUIRE(x && wpk4 && y, "tcx_convT2x: null pointer");
+    TCX_REQUIRE(Bt >= 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "tcx_convT2x: bad shape");
+    TCX_REQUIRE(act >= 0 && act <= 3, "tcx_convT2x: bad act");
     TCX_REQUIRE(cout_pad >= Cout && cout_pad % 32 == 0 && kpad % BK == 0 && kpad >= 4 * Cin, "tcx_convT2x: bad padding");
     for (int ph = 0; ph < 4; ++ph) {
         const int ry = ph >> 1, rx = ph & 1;

@@ -139,6 +139,11 @@ __global__ __launch_bounds__(256) void k_thin_cout1(ThinConv a) {
     }
 }
 
+// dynamic LDS of k_thin_cin1: the transposed weights, the bias and the ks staged rows
+size_t cin1_lds(const ThinConv& a) {
+    return ((size_t)a.ks * a.ks * a.Cout + a.Cout + (size_t)a.ks * (a.Wo + a.ks - 1)) * sizeof(float);
+}
+
 size_t cout1_lds(const ThinConv& a) {
     return ((size_t)a.ks * a.ks * a.Cin + (size_t)a.ks * a.W * ((a.Cin / 4) | 1)) * sizeof(float);
 }
@@ -149,7 +154,8 @@ size_t cout1_lds(const ThinConv& a) {
 bool thin_conv_takes(const ThinConv& a) {
     static const bool off = getenv("TCX_THIN") && getenv("TCX_THIN")[0] == '0';  // A/B: the MFMA kernels
     if (off || a.ks < 1 || a.ks > 7 || a.B <= 0 || (size_t)a.B * a.Ho >= (1u << 31)) return false;
-    if (a.Cin == 1 && a.Cout % 4 == 0 && a.ks * a.ks * a.Cout <= 8192 && a.Wo + a.ks - 1 <= 4096 && aligned16(a.y) &&
+    if (a.Cin == 1 && a.Cout % 4 == 0 && a.ks * a.ks * a.Cout <= 8192 && a.Wo + a.ks - 1 <= 4096 && cin1_lds(a) <= 48 * 1024 &&
+        aligned16(a.y) &&
         (!a.resid || aligned16(a.resid)) && (!a.bias_b || aligned16(a.bias_b)))
         return true;
     return a.Cout == 1 && a.Cin % 4 == 0 && cout1_lds(a) <= 48 * 1024 && aligned16(a.x) && aligned16(a.w);
@@ -157,9 +163,7 @@ bool thin_conv_takes(const ThinConv& a) {
 
 int launch_thin_conv(const ThinConv& a, hipStream_t st) {
     if (a.Cin == 1) {
-        hipLaunchKernelGGL(k_thin_cin1, dim3(std::min(a.B * a.Ho, 2048)), dim3(256),
-                           ((size_t)a.ks * a.ks * a.Cout + a.Cout + (size_t)a.ks * (a.Wo + a.ks - 1)) * sizeof(float), st,
-                           a);
+        hipLaunchKernelGGL(k_thin_cin1, dim3(std::min(a.B * a.Ho, 2048)), dim3(256), cin1_lds(a), st, a);
     } else {
         hipLaunchKernelGGL(k_thin_cout1, dim3(std::min(a.B * a.Ho, 2048)), dim3(256), cout1_lds(a), st, a);
     }
