@@ -54,11 +54,16 @@ constexpr int M_PAIR = 12288;          // bytes of B fragments per tap pair (2 t
 constexpr int M_BN = 96;               // output channels per tile
 
 __host__ __device__ constexpr int m_npx(int W) { return (M_TP / W + 2) * (W + 2); }
-// PRO 1: + the image's GroupNorm tables [scale | shift][Cin <= 384] after the ring
-template <int W, int PRO = 0>
+// PRO 1: + the image's GroupNorm tables [scale | shift][Cin <= 384] after the ring; VT: + the halo
+// slots' DMA byte offsets after them, 16 dwords per instruction, both halo waves' NIH instructions
+// (2 NIH >= NI: every read of the table stays inside it; 1,664 B at 64-px rows: 80,512 B, two workgroups
+// per CU's 160 KB)
+template <int W, int PRO = 0, bool VT = false>
 constexpr size_t conv3m_lds_bytes() {
-    return (size_t)2 * ((m_npx(W) + 15) / 16) * 16 * 64 + 2 * (size_t)M_PAIR + (PRO == 1 ? 2 * 384 * sizeof(float) : 0);
+    return (size_t)2 * ((m_npx(W) + 15) / 16) * 16 * 64 + 2 * (size_t)M_PAIR + (PRO == 1 ? 2 * 384 * sizeof(float) : 0) +
+           (VT ? (size_t)2 * (((m_npx(W) + 15) / 16 + 1) / 2) * 16 * sizeof(int) : 0);
 }
+static_assert(conv3m_lds_bytes<64, 1, true>() <= 80 * 1024, "k_conv3m: two workgroups per CU");
 // PRO 1 transform units per thread: the 2 NPX 8-channel halo units of a chunk over 256 threads
 __host__ __device__ constexpr int m_tu(int W) { return (2 * m_npx(W) + 255) / 256; }
 // PRO 1 transform lane map (found by search over the ds_read_b128 16-lane groups and the ds_write_b128
@@ -120,8 +125,20 @@ constexpr int M_WAIT_LGKM0 = 0xC07F;  // s_waitcnt lgkmcnt(0)
 // values, four channel-pair splits and two ds_write_b128 spread one task per MFMA gap over the half's
 // 36 MFMAs.  It is published by the same barriers as an h2 chunk (mids 8 / 3), so the MFMA pipeline,
 // the weight ring and the epilogue are k_conv3m's.
-template <int W, bool FAST, int PRO>
+// VT (PRO 1): a halo lane's DMA byte offsets do not depend on the chunk (the chunk rides in the
+// instruction's scalar offset), so the halo waves compute them once, park them in LDS and reload them
+// at each issue (one ds_read_b32 in front of the buffer_load) instead of recomputing ~22 VALU with an
+// integer multiply per issue beside the MFMAs; and every value of the transform passes through an
+// opaque register between its tasks, so that the SLP vectoriser cannot pack two values' fma / multiply
+// into v_pk_*_f32 across the schedule's fences (packed f32 beside MFMAs costs more than two scalar
+// ops; the packing also merged the value tasks of two gaps, so kMSched was not what ran).  Same
+// addresses and the same IEEE operations, the compiler's contraction of the split's residual included
+// (t_pair): outputs are bit-equal to the VT = false form, which TCX_CONV3M_PRO1_TAB=0 selects (A/B runs
+// and tests/test_gpu_conv3m_pro1.py).  Loop VALU per 9-pair trip 1,118 -> 630 at 64-px rows, 910 -> 478
+// at 32 / 16 (tools/loop_valu_mix.py, tests/test_conv3m_loop_mix_cpu.py; OPTLOG 3o)
+template <int W, bool FAST, int PRO, bool VT = false>
 __global__ __launch_bounds__(64 * M_NW, 2) void k_conv3m(ConvParams p) {
+    static_assert(!VT || PRO == 1, "k_conv3m: the offset table is the GroupNorm-prologue form's");
     constexpr int W2 = W + 2;
     constexpr int NPX = m_npx(W);
     constexpr int NI = (NPX + 15) / 16;  // halo DMA instructions per chunk (16 slots each)
@@ -129,6 +146,7 @@ __global__ __launch_bounds__(64 * M_NW, 2) void k_conv3m(ConvParams p) {
     constexpr int HB = NI * 16 * 64;
     constexpr int RING = 2 * HB;
     constexpr int TAB = RING + 2 * M_PAIR;  // PRO 1: [scale | shift][Cin]
+    constexpr int TABV = TAB + 2 * 384 * 4;  // VT: [2 NIH instructions][16 halo slots] DMA byte offsets
     constexpr int TU = m_tu(W);             // PRO 1: transform units per thread and chunk (3 or 4)
     static_assert(W == 16 || W == 32 || W == 64, "k_conv3m: rows of 16, 32 or 64 pixels");
     static_assert(NI * 16 >= NPX + 4, "k_conv3m: idle transform lanes use 4 padding slots");
@@ -180,7 +198,8 @@ __global__ __launch_bounds__(64 * M_NW, 2) void k_conv3m(ConvParams p) {
         // PRO 1 at 64-px rows: recomputed at every issue (an opaque copy of the lane index keeps hipcc from
         // hoisting all 13 offsets out of the tap loop, where they spilled with the transform's registers)
         int ls = lane >> 2;
-        if constexpr (PRO == 1) asm volatile("v_mov_b32 %0, %1" : "=v"(ls) : "v"(lane >> 2));
+        // (VT: computed once, in the prologue)
+        if constexpr (PRO == 1 && !VT) asm volatile("v_mov_b32 %0, %1" : "=v"(ls) : "v"(lane >> 2));
         const int hr0 = (16 * i) / W2;
         const int th = W2 * (hr0 + 1) - 16 * i;
         const int y0 = wrap_idx(r0 + hr0 - 1, H), y1 = wrap_idx(r0 + hr0, H);
@@ -218,6 +237,33 @@ __global__ __launch_bounds__(64 * M_NW, 2) void k_conv3m(ConvParams p) {
     auto halo_all = [&](int j, int buf) __attribute__((always_inline)) {
 #pragma unroll
         for (int t3 = 0; t3 < 3; ++t3) halo_third(j, buf, t3);
+    };
+    // VT: chunk j's raw halo into buffer buf with the offsets reloaded from the LDS table.  A slot's four
+    // lanes differ only in the 16-B piece, (l % 4) ^ sw(col): the table holds one entry per slot (16 NI
+    // dwords), pixel offset + 16 sw(col) (the pixel offset is a multiple of 128: Cin % 32 == 0), and the
+    // lane's offset is entry ^ 16 (l % 4), one VALU per issue.  The reads are inline asm with their own
+    // lgkmcnt wait (the transform's lds_rd16 note: a C++ LDS read after an LDS-DMA issue waits for
+    // vmcnt(0)); nothing else of this wave is in flight on lgkmcnt at the mids that issue a chunk
+    const int lds_base = (int)(size_t)((__attribute__((address_space(3))) char*)smc);
+    auto halo_tab = [&](int j, int buf) __attribute__((always_inline)) {
+        // the table address and the piece from the lane index, recounted per chunk (opaque, or it is
+        // hoisted): kept in registers across the tap loop they spilled beside the transform's
+        int lo;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lo));
+        const int vta = lds_base + TABV + (16 * hw + (lo >> 2)) * 4;  // slot 16 (2 q + hw) + l / 4: + 128 q
+        const int vpc = 16 * (lo & 3);
+        int v[NIH];
+#pragma unroll
+        for (int q = 0; q < NIH; ++q) asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v[q]) : "v"(vta), "i"(q * 128));
+        // (as with lds_rd16, this assumes the compiler leaves v[q] where the read put it until the wait:
+        // nothing between the asm statements gives it a reason to copy; the pin below orders every use)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int q = 0; q < NIH; ++q) {
+            asm volatile("" : "+v"(v[q]));  // used after the wait
+            const int i = 2 * q + hw;
+            if (i < NI) m_dma16(r1, smd + buf * HB + i * 1024, v[q] ^ vpc, j * M_KC * 4);
+        }
     };
     // weight pair k (12 KB) -> ring slot k & 1; wave w (0, 1) moves KB [6 w, 6 w + 6)
     auto pair_issue = [&](int k) __attribute__((always_inline)) {
@@ -291,10 +337,19 @@ __global__ __launch_bounds__(64 * M_NW, 2) void k_conv3m(ConvParams p) {
     auto t_addr = [&](int i) __attribute__((always_inline)) {
         const int sl0 = 128 * i + 32 * wv + t_so;
         tlive = sl0 < NPX;
-        const int sl = tlive ? sl0 : NPX + (lane & 3);
+        const int sl = tlive ? sl0 : NPX + (VT ? 2 * t_g + (t_so & 1) : lane & 3);  // VT: lane & 3 without the lane
         tdst = sl * 64 + 16 * ((2 * t_g) ^ sw(sl % W2));
     };
     auto t_tab = [&](int q) __attribute__((always_inline)) {  // channels 2 q, 2 q + 1 of the lane's group
+        if constexpr (VT) {
+            // the chunk's two table rows as opaque scalars: one lane term (32 t_g) serves both, where the
+            // compiler kept a VGPR per row (lane term + row) across the tap loop and spilled one
+            int ra = TAB + tj * (M_KC * 4), rb = ra + p.C1 * 4;
+            asm volatile("" : "+s"(ra), "+s"(rb));
+            tsc[q & 1] = *reinterpret_cast<const f32x2*>(smc + (ra + 32 * t_g) + 8 * q);
+            tsh[q & 1] = *reinterpret_cast<const f32x2*>(smc + (rb + 32 * t_g) + 8 * q);
+            return;
+        }
         const float* t = Tw + tj * M_KC + 8 * t_g + 2 * q;
         tsc[q & 1] = *reinterpret_cast<const f32x2*>(t);
         tsh[q & 1] = *reinterpret_cast<const f32x2*>(t + p.C1);
@@ -304,7 +359,6 @@ __global__ __launch_bounds__(64 * M_NW, 2) void k_conv3m(ConvParams p) {
     // waves on the pair they had just issued, one L2 round trip per transform half); the halo buffer a
     // unit rewrites is never a DMA target while it is transformed (the raw chunk landed at the previous
     // mid), so the reads need only lgkmcnt, which t_val 0's explicit wait provides
-    const int lds_base = (int)(size_t)((__attribute__((address_space(3))) char*)smc);
     auto lds_rd16 = [&](int a) __attribute__((always_inline)) {
         f32x4 v;
         asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(a));
@@ -323,25 +377,42 @@ __global__ __launch_bounds__(64 * M_NW, 2) void k_conv3m(ConvParams p) {
         t_tab(0);
     };
     float ue[2];  // exp2 of value k between its parts A and B
+    // VT: the value leaves each part through an opaque register (no instruction), which ends the SLP
+    // vectoriser's tree there: two values' fma / multiply / residual stay scalar in their own gaps
+    auto t_opq = [&](float v) __attribute__((always_inline)) {
+        if constexpr (VT) asm volatile("" : "+v"(v));
+        return v;
+    };
     auto t_valA = [&](int k) __attribute__((always_inline)) {
         if (k == 0) __builtin_amdgcn_s_waitcnt(M_WAIT_LGKM0);  // the unit's asm reads (t_load)
         const int q = k >> 1, e = k & 1;
-        ux[k] = fmaf(ux[k], tsc[q & 1][e], tsh[q & 1][e]);  // u = -log2(e) t (the tables' staging)
+        ux[k] = t_opq(fmaf(ux[k], tsc[q & 1][e], tsh[q & 1][e]));  // u = -log2(e) t (the tables' staging)
         ue[k & 1] = __builtin_amdgcn_exp2f(ux[k]);
     };
-    auto t_valB = [&](int k) __attribute__((always_inline)) { ux[k] = ux[k] * __builtin_amdgcn_rcpf(1.0f + ue[k & 1]); };
+    // VT: part B leaves u and the reciprocal; t_pair forms the product and, as the compiler contracts it
+    // in the other form, the residual u rcp - h with one rounding (fma), both from scalar operations
+    auto t_valB = [&](int k) __attribute__((always_inline)) {
+        if constexpr (VT) ue[k & 1] = __builtin_amdgcn_rcpf(1.0f + ue[k & 1]);
+        else ux[k] = ux[k] * __builtin_amdgcn_rcpf(1.0f + ue[k & 1]);
+    };
     auto t_val = [&](int k) __attribute__((always_inline)) {
         t_valA(k);
         t_valB(k);
     };
     auto t_pair = [&](int q) __attribute__((always_inline)) {
-        const f32x2 v = {ux[2 * q], ux[2 * q + 1]};
+        f32x2 v = {ux[2 * q], ux[2 * q + 1]};
+        if constexpr (VT) v = (f32x2){t_opq(ux[2 * q] * ue[0]), t_opq(ux[2 * q + 1] * ue[1])};
         const f16x2 h = __builtin_convertvector(v, f16x2);
-        const f32x2 r = v - __builtin_convertvector(h, f32x2);
+        f32x2 r;
+        if constexpr (VT)
+            r = (f32x2){t_opq(fmaf(ux[2 * q], ue[0], -(float)h[0])), t_opq(fmaf(ux[2 * q + 1], ue[1], -(float)h[1]))};
+        else r = v - __builtin_convertvector(h, f32x2);  // contracted with part B's product: fma(u, rcp, -h)
         const f16x2 l = __builtin_convertvector(r, f16x2);
         uh[q] = __builtin_bit_cast(unsigned, h);
         ul[q] = __builtin_bit_cast(unsigned, l);
-        um = fmaxf(um, fmaxf(fabsf(v[0]), fabsf(v[1])));
+        // VT: one v_max3 (fmaxf of the opaque values would first canonicalise each: a v_max x, x per value)
+        if constexpr (VT) asm volatile("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(um) : "v"(v[0]), "v"(v[1]));
+        else um = fmaxf(um, fmaxf(fabsf(v[0]), fabsf(v[1])));
     };
     auto t_store = [&](int buf, bool live) __attribute__((always_inline)) {
         const int lb = lds_base + buf * HB;
@@ -383,6 +454,18 @@ __global__ __launch_bounds__(64 * M_NW, 2) void k_conv3m(ConvParams p) {
     if (wv < 2) {
         pair_issue(0);
         pair_issue(1);
+    } else if constexpr (VT) {
+        // the lane's offsets, once: into the table (before this wave's first DMA issue), then chunk 0 from them
+        int* const tv = reinterpret_cast<int*>(smc + TABV) + 16 * hw + (lane >> 2);
+        int hv[NIH];
+#pragma unroll
+        for (int q = 0; q < NIH; ++q) {
+            hv[q] = halo_voff(2 * q + hw, rowb, 32);
+            tv[q * 32] = hv[q] ^ (16 * (lane & 3));  // a slot's four lanes write the same entry (i >= NI: read, not issued)
+        }
+#pragma unroll
+        for (int q = 0; q < NIH; ++q)
+            if (2 * q + hw < NI) m_dma16(r1, smd + (2 * q + hw) * 1024, hv[q], 0);
     } else {
         halo_all(0, 0);
     }
@@ -402,7 +485,10 @@ __global__ __launch_bounds__(64 * M_NW, 2) void k_conv3m(ConvParams p) {
     __builtin_amdgcn_s_barrier();
     if (stamp) ts[1] = __builtin_amdgcn_s_memrealtime();
     if constexpr (PRO == 1) {
-        if (wv >= 2) halo_all(1, 1);  // cpt >= 2
+        if (wv >= 2) {  // cpt >= 2
+            if constexpr (VT) halo_tab(1, 1);
+            else halo_all(1, 1);
+        }
         tj = 0;
 #pragma unroll
         for (int i = 0; i < TU; ++i) {
@@ -485,9 +571,15 @@ __global__ __launch_bounds__(64 * M_NW, 2) void k_conv3m(ConvParams p) {
         } else if constexpr (PRO == 1) {
             // (the raw chunk in two parts over mids 4-5 / 8-0 measured no faster: r05_c)
             if constexpr (q == 4) {     // chunk 2 pp + 2 -> buffer 0 (chunk 2 pp was last read by pair 4)
-                if (2 * pp + 2 < cpt) halo_all(2 * pp + 2, 0);
+                if (2 * pp + 2 < cpt) {
+                    if constexpr (VT) halo_tab(2 * pp + 2, 0);
+                    else halo_all(2 * pp + 2, 0);
+                }
             } else if constexpr (q == 8) {     // chunk 2 pp + 3 -> buffer 1 (chunk 2 pp + 1 last read by pair 8)
-                if (2 * pp + 3 < cpt) halo_all(2 * pp + 3, 1);
+                if (2 * pp + 3 < cpt) {
+                    if constexpr (VT) halo_tab(2 * pp + 3, 1);
+                    else halo_all(2 * pp + 3, 1);
+                }
             }
         } else {
             if constexpr (q >= 4 && q <= 6) {  // chunk 2 pp + 2 -> buffer 0 (chunk 2 pp was last read by pair 4)
@@ -649,18 +741,30 @@ bool conv3m_oh2_enabled() {
     return on;
 }
 
+// TCX_CONV3M_PRO1_TAB=0: the GroupNorm-prologue form without the LDS offset table and with the
+// compiler's packed transform arithmetic (VT false: the form before the table; A/B and bit-equality tests)
+bool conv3m_pro1_tab_enabled() {
+    static const bool on = [] {
+        const char* e = getenv("TCX_CONV3M_PRO1_TAB");
+        return !(e && e[0] == '0');
+    }();
+    return on;
+}
+
 template <int W>
 int launch3m(const ConvParams& p, hipStream_t st) {
-    static bool attr[5] = {};
+    static bool attr[6] = {};
     const bool pro = p.sc1 != nullptr;
+    const bool vt = pro && conv3m_pro1_tab_enabled();
     const bool fast = p.act == 0 && !p.out_h2;
     const bool oh2 = p.act == 0 && p.out_h2 && !p.cm2 && conv3m_oh2_enabled();  // PRO 3: h2 output, no act
-    const int ai = pro ? 2 : p.cm2 ? 3 : oh2 ? 4 : (int)fast;
-    void (*const k)(ConvParams) = pro ? &k_conv3m<W, true, 1>
+    const int ai = vt ? 5 : pro ? 2 : p.cm2 ? 3 : oh2 ? 4 : (int)fast;
+    void (*const k)(ConvParams) = vt ? &k_conv3m<W, true, 1, true>
+                                  : pro ? &k_conv3m<W, true, 1>
                                   : p.cm2 ? &k_conv3m<W, true, 2>
                                   : oh2 ? &k_conv3m<W, true, 3>
                                   : fast ? &k_conv3m<W, true, 0> : &k_conv3m<W, false, 0>;
-    const size_t lds = pro ? conv3m_lds_bytes<W, 1>() : conv3m_lds_bytes<W, 0>();
+    const size_t lds = vt ? conv3m_lds_bytes<W, 1, true>() : pro ? conv3m_lds_bytes<W, 1>() : conv3m_lds_bytes<W, 0>();
     if (!attr[ai]) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
             hipSuccess) {
