@@ -396,6 +396,14 @@ int tcx_debug_fail_eval(int k);
  * GroupNorm partials to the fp32 rounding of their per-lane sums). */
 int tcx_debug_conv3mb(int mode);
 
+/* Test hook: the earlier forms of three memory passes of the split-path U-Net on this host thread.  A set bit
+ * selects the form from before the index decode was taken out of the pass — bit 0 the first conv's record
+ * kernel (k_conv_first_rec instead of its C0 = 96, W = 64 form), bit 1 the banded x2 upsample (the run-time
+ * shape form instead of the 16 x 192 / 32 x 96 ones), bit 2 the register head's reduction (__shfl_xor instead
+ * of DPP adds).  0 (the default) runs the new forms.  Returns the previous mask.  Both forms evaluate the same
+ * expressions on the same values: records, range flag and eps are bit-identical. */
+int tcx_debug_pass_forms(int mask);
+
 /* Test hook (round 6): the calling thread's choice for the halo-staged 3x3 weight gradient of
  * tcx_conv_wgrad_h2 (wgrad3h.hip: all nine taps of a 32-channel group per workgroup): -1 default
  * (on; TCX_WGRAD3H=0 turns it off), 0 = k_wgrad_h2, 1 = the halo kernel.  Returns the previous mode. */

@@ -361,12 +361,23 @@ __global__ __launch_bounds__(256) void k_upsample2x_g8(const float* __restrict__
 constexpr int UB_MAXWC = 3072;             // W * C of one source row (72 KB of LDS for an 8-row band)
 // ROWS output rows per band (ROWS / 2 + 2 source rows staged); G8: one 8-channel group per item (two
 // 16-B stores) instead of one 4-channel quad (two 8-B stores)
-template <int ROWS, bool G8>
+// WT, CT (> 0: the 64^2 U-Net's us2 / us1 sources, 16 x 192 and 32 x 96; needs ROWS = 4, G8, bf = 0): W and C as
+// compile-time constants.  Both shapes have 768 float4 per source row and 768 (ox, group) columns per output
+// row, three per thread: phase 1's row / channel decode folds into constants, and phase 2 — 220 VALU per
+// record in the run-time form, 19 integer multiplies and the float coordinate math among them, VALU-issue
+// bound — keeps a thread on its 3 columns over the band's 4 rows (the column decode and x0 / x1 / lx once per
+// column, (y0, y1, ly) once per row and wave-uniform) and computes the horizontal pair fmaf(lx1, v(x1),
+// lx0 v(x0)) of each staged row once instead of once per output row that reads it (16 ds_read_b128 per 4
+// records, not 32).  The same expressions on the same values: bit-identical records and range flag.
+template <int ROWS, bool G8, int WT = 0, int CT = 0>
 __global__ __launch_bounds__(256, 2) void k_upsample2x_band(const float* __restrict__ x, char* __restrict__ y, int H,
-                                                           int W, int C, const float* __restrict__ tsc,
-                                                           const float* __restrict__ tsh, unsigned* ovf, int bf) {
+                                                           int W_, int C_, const float* __restrict__ tsc,
+                                                           const float* __restrict__ tsh, unsigned* ovf, int bf_) {
+    constexpr bool FX = WT > 0;
+    static_assert(!FX || (ROWS == 4 && G8 && WT * CT == 4 * 768 && CT % 8 == 0), "the fixed-shape form's columns");
     constexpr int SRC = ROWS / 2 + 2;
     extern __shared__ __attribute__((aligned(16))) float ub[];  // [SRC][W][C]
+    const int W = FX ? WT : W_, C = FX ? CT : C_, bf = FX ? 0 : bf_;
     const int nband = 2 * H / ROWS;
     const int b = blockIdx.x / nband, band = blockIdx.x - (blockIdx.x / nband) * nband;
     const int ys0 = band * (ROWS / 2) - 1;  // source row of LDS row 0 (before clamping)
@@ -378,7 +389,8 @@ __global__ __launch_bounds__(256, 2) void k_upsample2x_band(const float* __restr
     for (int k = 0; k < NL; ++k) {
         const int i = threadIdx.x + 256 * k;
         if (i < SRC * WC4) {
-            const int r = i / WC4, e = i - (i / WC4) * WC4;
+            // (fixed shape: 768 = 3 x 256 float4 per row, so the row is k / 3)
+            const int r = FX ? k / 3 : i / WC4, e = FX ? (int)threadIdx.x + 256 * (k % 3) : i - (i / WC4) * WC4;
             const int ysrc = min(max(ys0 + r, 0), H - 1);
             v[k] = *reinterpret_cast<const f4v*>(x + ((size_t)b * H + ysrc) * WC + 4 * e);
         }
@@ -388,7 +400,14 @@ __global__ __launch_bounds__(256, 2) void k_upsample2x_band(const float* __restr
         const int i = threadIdx.x + 256 * k;
         if (i < SRC * WC4) {
             if (tsc) {
-                const int c4 = (i - (i / C4) * C4) * 4;
+                int c4;
+                if constexpr (FX) {  // i % C4 from threadIdx.x % C4 and a constant
+                    constexpr int Q4 = CT / 4;
+                    const int c = (int)threadIdx.x % Q4 + (256 * k) % Q4;
+                    c4 = (c >= Q4 ? c - Q4 : c) * 4;
+                } else {
+                    c4 = (i - (i / C4) * C4) * 4;
+                }
                 const f4v s4 = *reinterpret_cast<const f4v*>(tsc + (size_t)b * C + c4);
                 const f4v h4 = *reinterpret_cast<const f4v*>(tsh + (size_t)b * C + c4);
 #pragma unroll
@@ -404,6 +423,78 @@ __global__ __launch_bounds__(256, 2) void k_upsample2x_band(const float* __restr
     // phase 2: output items (oy, ox, quad or group), channel index fastest
     bool bad = false;
     constexpr int CW = G8 ? 8 : 4;  // channels per item
+    if constexpr (FX) {
+        constexpr int CI = CT / 8;
+        // the rows' (y0, y1, ly): as the run-time form computes them.  Output row 4 band + ry reads the staged
+        // rows (0, 1) [(1, 2) in band 0, whose row -1 clamps to 0], (1, 2), (1, 2), (2, 3) [(2, 2) in the last band]
+        int ra[ROWS], rb[ROWS];
+        float ly0[ROWS], ly1[ROWS];
+#pragma unroll
+        for (int ry = 0; ry < ROWS; ++ry) {
+            const int oy = band * ROWS + ry;
+            float sy = 0.5f * ((float)oy + 0.5f) - 0.5f;
+            sy = sy < 0.f ? 0.f : sy;
+            const int y0 = (int)sy;
+            const int y1 = y0 + (y0 < H - 1 ? 1 : 0);
+            ly1[ry] = sy - (float)y0;
+            ly0[ry] = 1.f - ly1[ry];
+            ra[ry] = y0 - ys0;
+            rb[ry] = y1 - ys0;
+        }
+        const bool first = ra[0] != 0, last = rb[ROWS - 1] != SRC - 1;  // wave-uniform
+        char* yb = y + ((size_t)b * 2 * H + (size_t)band * ROWS) * (2 * WT) * CT * 4;
+        // column (ox, group), group fastest: 768 per output row; the thread's are threadIdx.x + 256 j
+        int q = (int)threadIdx.x % CI, ox = (int)threadIdx.x / CI;
+        char* gp = yb + (size_t)threadIdx.x * 32;
+#pragma unroll 1
+        for (int j = 0; j < 3; ++j) {
+            float sx = 0.5f * ((float)ox + 0.5f) - 0.5f;
+            sx = sx < 0.f ? 0.f : sx;
+            const int x0 = (int)sx, x1 = x0 + (x0 < WT - 1 ? 1 : 0);
+            const float lx1 = sx - (float)x0, lx0 = 1.f - lx1;
+            const float* c0 = ub + __mul24(x0, CT) + 8 * q;  // (x0, x1 < WT: the full-rate 24-bit multiply)
+            const float* c1 = ub + __mul24(x1, CT) + 8 * q;
+            float hp[SRC][8];  // the horizontal pair of each staged row
+#pragma unroll
+            for (int r = 0; r < SRC; ++r)
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const f4v va = *reinterpret_cast<const f4v*>(c0 + r * (WT * CT) + 4 * h);
+                    const f4v vb = *reinterpret_cast<const f4v*>(c1 + r * (WT * CT) + 4 * h);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) hp[r][4 * h + e] = fmaf(lx1, vb[e], lx0 * va[e]);
+                }
+            auto emit = [&](int ry, const float(&h0)[8], const float(&h1)[8]) __attribute__((always_inline)) {
+                float o[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    o[e] = fmaf(ly1[ry], h1[e], ly0[ry] * h0[e]);
+                    bad = bad || h2_bad(o[e]);
+                }
+                uint2 hi[2], lo[2];
+                split4x(make_float4(o[0], o[1], o[2], o[3]), hi[0], lo[0], false);
+                split4x(make_float4(o[4], o[5], o[6], o[7]), hi[1], lo[1], false);
+                char* p = gp + (size_t)ry * (2 * WT * CT * 4);
+                *reinterpret_cast<uint4*>(p) = make_uint4(hi[0].x, hi[0].y, hi[1].x, hi[1].y);
+                *reinterpret_cast<uint4*>(p + 16) = make_uint4(lo[0].x, lo[0].y, lo[1].x, lo[1].y);
+            };
+            if (first) emit(0, hp[1], hp[2]);
+            else emit(0, hp[0], hp[1]);
+            emit(1, hp[1], hp[2]);
+            emit(2, hp[1], hp[2]);
+            if (last) emit(3, hp[2], hp[2]);
+            else emit(3, hp[2], hp[3]);
+            gp += 256 * 32;
+            q += 256 % CI;
+            ox += 256 / CI;
+            if (q >= CI) {
+                q -= CI;
+                ox += 1;
+            }
+        }
+        h2_flag(ovf, bad);
+        return;
+    }
     const int CI = C / CW;
     const int nq = ROWS * 2 * W * CI;
     for (int i = threadIdx.x; i < nq; i += 256) {
@@ -1124,6 +1215,11 @@ extern "C" int tcx_upsample2x(const float* x, float* y, int Bt, int H, int W, in
 }
 
 namespace tcx {
+// tcx_debug_pass_forms (tests, A/B): a set bit selects the form before the decode-free one on this host thread —
+// bit 0 k_conv_first_rec96, bit 1 the fixed-shape k_upsample2x_band, bit 2 k_head8r's DPP reduction (unet.hip)
+thread_local int g_pass_forms = 0;
+int pass_forms() { return g_pass_forms; }
+
 // the banded upsample covers this source shape (its band of source rows fits the LDS)
 bool upsample_band_ok(int H, int W, int C) { return H % 2 == 0 && W * C <= UB_MAXWC && C % 8 == 0; }
 // source columns per segment of the column-segmented band (0: none fits): the widest power of two
@@ -1148,15 +1244,18 @@ int upsample2x_h2(const float* x, void* y, int Bt, int H, int W, int C, const fl
         // items were 3-28 % slower; r05_n: 2-row bands, 36 KB and 4 per CU, 4-7 % slower)
         constexpr int rows = 4;
         const size_t shm = (size_t)(rows / 2 + 2) * W * C * sizeof(float);
-        const auto k = &k_upsample2x_band<4, true>;
-        static bool attr = false;
-        if (!attr) {
+        // the fixed-shape forms (us2 / us1 of the 64^2 U-Net, h2 records); tcx_debug_pass_forms bit 1: the run-time form
+        const int fx = (bf != 0 || (pass_forms() & 2)) ? 0 : (W == 16 && C == 192) ? 1 : (W == 32 && C == 96) ? 2 : 0;
+        const auto k = fx == 1 ? &k_upsample2x_band<4, true, 16, 192>
+                               : fx == 2 ? &k_upsample2x_band<4, true, 32, 96> : &k_upsample2x_band<4, true>;
+        static bool attr[3] = {false, false, false};
+        if (!attr[fx]) {
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)(4 * UB_MAXWC * sizeof(float))) != hipSuccess) {
                 set_error("tcx_upsample2x_h2: cannot enable %zu B of dynamic LDS", 4 * UB_MAXWC * sizeof(float));
                 return TCX_EHIP;
             }
-            attr = true;
+            attr[fx] = true;
         }
         hipLaunchKernelGGL(k, dim3(Bt * (2 * H / rows)), dim3(256), shm, st, x, (char*)y, H, W, C, scale, shift, ovf, bf);
         return check_launch("tcx_upsample2x_h2(band)");
@@ -1330,6 +1429,14 @@ int attn_prep_h2(float* a, void* y, int Bt, int HW, int C, const float* sc, cons
     return check_launch("attn_prep_h2");
 }
 }  // namespace tcx
+
+// Test hook: which of the first conv (bit 0), the upsample (bit 1) and the head (bit 2) run their earlier form
+// on this host thread.  Returns the previous mask.
+extern "C" int tcx_debug_pass_forms(int mask) {
+    const int prev = tcx::g_pass_forms;
+    tcx::g_pass_forms = mask & 7;
+    return prev;
+}
 
 extern "C" int tcx_upsample2x_h2(const float* x, void* y, int Bt, int H, int W, int C, const float* scale,
                                  const float* shift, unsigned* ovf, void* stream) {

@@ -24,6 +24,7 @@ bool upsample_fused_ok(int H, int W, int C);  // norm.hip: band / segmented band
 bool attn_prep_ok(int HW, int C, int groups, int bf);  // norm.hip: the attention input pass
 int attn_prep_h2(float* a, void* y, int Bt, int HW, int C, const float* sc, const float* sh, const float* gamma,
                  const float* beta, int groups, unsigned* ovf, int bf, hipStream_t st);
+int pass_forms();  // norm.hip: tcx_debug_pass_forms' mask (bit 0 first conv, 1 upsample, 2 head: the older form)
 int upsample2x_h2(const float* x, void* y, int Bt, int H, int W, int C, const float* scale, const float* shift,
                   unsigned* ovf, int bf, hipStream_t st);
 int gn_apply_tab_h2(const float* x, void* y, int Bt, int HW, int C, const float* scale, const float* shift, int silu,
@@ -569,7 +570,15 @@ __device__ __forceinline__ float4 head_ld4(const float* h, size_t e) {
 // LA: passes whose loads are in flight ahead of the one being computed (round 5: 2 -> 4, the whole pass
 // loop unrolled so the ring is static; 2 passes ahead left the 403 MB read at 3.8 TB/s)
 constexpr int HR_LA = 4;
-template <int Q, bool B2 = false>
+// a + (a of the lane that DPP control CTRL names): an 8-lane group's xor-shuffle sum without the LDS
+// crossbar (ds_bpermute: an address, an LDS round trip and a wait per stage)
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float a) {
+    // (every lane reads a lane of its own row: bound_ctrl only lets the move fold into the add's DPP operand)
+    return a + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(a), CTRL, 0xf, 0xf, true));
+}
+// SHFL: the three reduction stages as __shfl_xor (the form before the DPP adds; tcx_debug_pass_forms bit 2)
+template <int Q, bool B2 = false, bool SHFL = false>
 __global__ __launch_bounds__(256) void k_head8r(const float* __restrict__ h, int HW, const float* __restrict__ tsc,
                                                 const float* __restrict__ tsh, const float* __restrict__ w_out,
                                                 float* __restrict__ r) {
@@ -666,9 +675,18 @@ __global__ __launch_bounds__(256) void k_head8r(const float* __restrict__ h, int
         }
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
-            acc[t] += __shfl_xor(acc[t], 1);
-            acc[t] += __shfl_xor(acc[t], 2);
-            acc[t] += __shfl_xor(acc[t], 4);
+            if constexpr (SHFL) {
+                acc[t] += __shfl_xor(acc[t], 1);
+                acc[t] += __shfl_xor(acc[t], 2);
+                acc[t] += __shfl_xor(acc[t], 4);
+            } else {
+                // quad_perm [1,0,3,2] and [2,3,0,1] are lanes ^ 1 and ^ 2.  Every lane of a quad then holds the
+                // quad's sum, so lane 7 - i of the 8-lane group (row_half_mirror) carries what lane i ^ 4 does:
+                // the operands of each add are those of the shuffles (an fp32 add commutes: the same bits)
+                acc[t] = dpp_add<0xB1>(acc[t]);
+                acc[t] = dpp_add<0x4E>(acc[t]);
+                acc[t] = dpp_add<0x141>(acc[t]);
+            }
         }
         const int p = pg - b * HW;
         float* dst = r + (size_t)b * 9 * HW + p;
@@ -775,6 +793,108 @@ __global__ __launch_bounds__(256) void k_conv_first_rec(const float* __restrict_
             char* gp = dst + (size_t)pl * C0 * 4 + 32 * g;
             *reinterpret_cast<uint4*>(gp) = make_uint4(hi0.x, hi0.y, hi1.x, hi1.y);
             *reinterpret_cast<uint4*>(gp + 16) = make_uint4(lo0.x, lo0.y, lo1.x, lo1.y);
+        }
+    }
+    h2_flag(ovf, bad);
+}
+
+// k_conv_first_rec at the 64^2 U-Net's shape (C0 = 96, W = 64, FR_PX pixels per workgroup, h2 records): the
+// generic kernel's record loop spends half of its ~315 VALU per record on decoding the item (item / G8,
+// p / W, three wrap_idx, the addresses of 9 x reads and 24 table reads) and is VALU-issue bound.  Here a
+// thread's items tid + 256 k advance by 4 groups (mod 12) and 21 pixels plus the carry, so the loop holds no
+// division or multiply; a wrapped column is an & 63 and every LDS read of a record is one of four bases
+// plus an immediate.  The same fmaf chains in the same order on the same values: bit-identical records
+// and range flag.
+__global__ __launch_bounds__(256) void k_conv_first_rec96(const float* __restrict__ x, int bmod, int H,
+                                                          const float* __restrict__ w0, int kpad,
+                                                          const float* __restrict__ bias_b, char* __restrict__ y,
+                                                          CondTab ct, int Bimg, int cfg, const float* __restrict__ tsc,
+                                                          const float* __restrict__ tsh, unsigned* ovf) {
+    constexpr int C0 = 96, W = 64, G8 = C0 / 8, NR = FR_PX / W + 2;
+    static_assert(NR * W == 256 && (FR_PX * G8) % 256 == 0 && 256 % G8 == 4, "item stride of the record loop");
+    __shared__ __attribute__((aligned(16))) float fr[12 * C0 + NR * W];  // w[9][C0] | bias | sc | sh | xr[NR][W]
+    float* w = fr;
+    float* bs = w + 9 * C0;
+    float* sc = bs + C0;
+    float* sh = sc + C0;
+    float* xr = sh + C0;
+    const int HW = H * W;
+    const int b = blockIdx.y;
+    const int tid = threadIdx.x;
+    const int p0 = blockIdx.x * FR_PX;
+    const int y0 = p0 / W;
+    const float* xb = x + (size_t)(b % bmod) * HW;
+    xr[tid] = xb[(size_t)wrap_idx(y0 - 1 + (tid >> 6), H) * W + (tid & (W - 1))];
+    for (int i = tid; i < 9 * C0; i += 256) {
+        const int co = i / 9, k = i - (i / 9) * 9;
+        w[k * C0 + co] = w0[(size_t)co * kpad + k];
+    }
+    const float* bb = ct.bias_img ? cond_bias_row(ct, b, Bimg, cfg, C0) : bias_b + (size_t)b * C0;
+    if (tid < C0) {
+        bs[tid] = bb[tid];
+        sc[tid] = tsc[(size_t)b * C0 + tid];
+        sh[tid] = tsh[(size_t)b * C0 + tid];
+    }
+    __syncthreads();
+    int g = tid % G8, pl = tid / G8;  // item = pl * G8 + g
+    int wo = 8 * g;                   // the group's column of w / bias / sc / sh
+    char* gp = y + ((size_t)b * HW + p0) * C0 * 4 + (size_t)tid * 32;
+    bool bad = false;
+#pragma unroll 1
+    for (int it = 0; it < FR_PX * G8 / 256; ++it) {
+        const int xx = pl & (W - 1), rb = pl - xx;  // pl = ry * W + xx: staged rows ry .. ry + 2
+        const float* xc = xr + pl;
+        const float* xl = xr + rb + ((xx - 1) & (W - 1));
+        const float* xn = xr + rb + ((xx + 1) & (W - 1));
+        float xv[9];
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy) {
+            xv[dy * 3 + 0] = xl[dy * W];
+            xv[dy * 3 + 1] = xc[dy * W];
+            xv[dy * 3 + 2] = xn[dy * W];
+        }
+        const float* wg = fr + wo;
+        float4 a0 = *reinterpret_cast<const float4*>(wg + 9 * C0);
+        float4 a1 = *reinterpret_cast<const float4*>(wg + 9 * C0 + 4);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const float4 u = *reinterpret_cast<const float4*>(wg + k * C0);
+            const float4 v = *reinterpret_cast<const float4*>(wg + k * C0 + 4);
+            a0.x = fmaf(u.x, xv[k], a0.x); a0.y = fmaf(u.y, xv[k], a0.y);
+            a0.z = fmaf(u.z, xv[k], a0.z); a0.w = fmaf(u.w, xv[k], a0.w);
+            a1.x = fmaf(v.x, xv[k], a1.x); a1.y = fmaf(v.y, xv[k], a1.y);
+            a1.z = fmaf(v.z, xv[k], a1.z); a1.w = fmaf(v.w, xv[k], a1.w);
+            // opaque registers (no instruction) end the SLP tree here: packed, the chains became 36 v_pk_fma_f32
+            // (two issue slots each) fed by ~70 v_mov that gather their operand pairs
+            asm volatile("" : "+v"(a0.x), "+v"(a0.y), "+v"(a0.z), "+v"(a0.w), "+v"(a1.x), "+v"(a1.y), "+v"(a1.z), "+v"(a1.w));
+        }
+        const float4 s0 = *reinterpret_cast<const float4*>(wg + 10 * C0);
+        const float4 s1 = *reinterpret_cast<const float4*>(wg + 10 * C0 + 4);
+        const float4 t0 = *reinterpret_cast<const float4*>(wg + 11 * C0);
+        const float4 t1 = *reinterpret_cast<const float4*>(wg + 11 * C0 + 4);
+        auto sl = [](float v, float scl, float shf) {
+            const float q = fmaf(v, scl, shf);
+            return q * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * q));
+        };
+        const float4 o0 = make_float4(sl(a0.x, s0.x, t0.x), sl(a0.y, s0.y, t0.y), sl(a0.z, s0.z, t0.z),
+                                      sl(a0.w, s0.w, t0.w));
+        const float4 o1 = make_float4(sl(a1.x, s1.x, t1.x), sl(a1.y, s1.y, t1.y), sl(a1.z, s1.z, t1.z),
+                                      sl(a1.w, s1.w, t1.w));
+        uint2 hi0, lo0, hi1, lo1;
+        split4x(o0, hi0, lo0, false);
+        split4x(o1, hi1, lo1, false);
+        bad = bad || h2_bad(o0.x) || h2_bad(o0.y) || h2_bad(o0.z) || h2_bad(o0.w) || h2_bad(o1.x) || h2_bad(o1.y) ||
+              h2_bad(o1.z) || h2_bad(o1.w);
+        *reinterpret_cast<uint4*>(gp) = make_uint4(hi0.x, hi0.y, hi1.x, hi1.y);
+        *reinterpret_cast<uint4*>(gp + 16) = make_uint4(lo0.x, lo0.y, lo1.x, lo1.y);
+        gp += 256 * 32;  // item + 256 = (pl + 21) * 12 + g + 4
+        g += 4;
+        pl += 21;
+        wo += 32;
+        if (g >= G8) {
+            g -= G8;
+            pl += 1;
+            wo -= 8 * G8;
         }
     }
     h2_flag(ovf, bad);
@@ -1271,9 +1391,13 @@ int unet_body(const tcx_unet* net, const Plan& P, const float* x, int B, const f
                     const int fpx = (W >= 256 && (H * W) % fr_wide == 0 && fr_wide % W == 0) ? fr_wide : FR_PX;
                     const int nrow = (fpx >= W ? fpx / W : 1) + 2;
                     const size_t shr = ((size_t)12 * C + (size_t)nrow * W) * sizeof(float);
-                    hipLaunchKernelGGL(k_conv_first_rec, dim3(H * W / fpx, Bt), dim3(256), shr, st, x, B, H, W, C,
-                                       c0.w, c0.kpad, P.bias0, (char*)P.a64, ct, B, cfg, P.sc(0), P.sh(0), h2.ovf,
-                                       fmt, fpx);
+                    if (C == 96 && W == 64 && fpx == FR_PX && fmt == 0 && !(pass_forms() & 1))
+                        hipLaunchKernelGGL(k_conv_first_rec96, dim3(H * W / FR_PX, Bt), dim3(256), 0, st, x, B, H, c0.w,
+                                           c0.kpad, P.bias0, (char*)P.a64, ct, B, cfg, P.sc(0), P.sh(0), h2.ovf);
+                    else
+                        hipLaunchKernelGGL(k_conv_first_rec, dim3(H * W / fpx, Bt), dim3(256), shr, st, x, B, H, W, C,
+                                           c0.w, c0.kpad, P.bias0, (char*)P.a64, ct, B, cfg, P.sc(0), P.sh(0), h2.ovf,
+                                           fmt, fpx);
                 } else {
                     hipLaunchKernelGGL(k_conv_first<2>, dim3(H * W / FIRST_PX, Bt), dim3(256), shm, st, x, B, H, W,
                                        C, c0.w, c0.kpad, P.bias0, P.a64, nullptr, ct, B, cfg, P.sc(0), P.sh(0),
@@ -1438,11 +1562,21 @@ int unet_body(const tcx_unet* net, const Plan& P, const float* x, int B, const f
         // register-weight head (r03_ag: 124 -> 118 us at 64^2); k_head8 for other widths / shapes
         if (P.P0 % HPR == 0 && (C == 96 || C == 64 || C == 32) && aligned16(net->out_w)) {  // (16-B constant loads)
             const dim3 gr(Bt * P.P0 / HPR);
-            if (C == 96 && fmt == 2)
-                hipLaunchKernelGGL((k_head8r<3, true>), gr, dim3(256), 0, st, P.a64, P.P0, P.sc(10), P.sh(10), net->out_w, P.r);
-            else if (C == 96) hipLaunchKernelGGL(k_head8r<3>, gr, dim3(256), 0, st, P.a64, P.P0, P.sc(10), P.sh(10), net->out_w, P.r);
-            else if (C == 64) hipLaunchKernelGGL(k_head8r<2>, gr, dim3(256), 0, st, P.a64, P.P0, P.sc(10), P.sh(10), net->out_w, P.r);
-            else hipLaunchKernelGGL(k_head8r<1>, gr, dim3(256), 0, st, P.a64, P.P0, P.sc(10), P.sh(10), net->out_w, P.r);
+            const bool shfl = (pass_forms() & 4) != 0;
+#define TCX_HEAD8R(Q, B2)                                                                                        \
+    do {                                                                                                         \
+        if (shfl)                                                                                                \
+            hipLaunchKernelGGL((k_head8r<Q, B2, true>), gr, dim3(256), 0, st, P.a64, P.P0, P.sc(10), P.sh(10),   \
+                               net->out_w, P.r);                                                                 \
+        else                                                                                                     \
+            hipLaunchKernelGGL((k_head8r<Q, B2, false>), gr, dim3(256), 0, st, P.a64, P.P0, P.sc(10), P.sh(10),  \
+                               net->out_w, P.r);                                                                 \
+    } while (0)
+            if (C == 96 && fmt == 2) TCX_HEAD8R(3, true);
+            else if (C == 96) TCX_HEAD8R(3, false);
+            else if (C == 64) TCX_HEAD8R(2, false);
+            else TCX_HEAD8R(1, false);
+#undef TCX_HEAD8R
             TCX_TRY(check_launch("k_head8r"));
         } else if (P.P0 % HP8 == 0 && (C == 96 || C == 64 || C == 128 || C == 32)) {
             const dim3 g8(Bt * P.P0 / HP8);
