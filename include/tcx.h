@@ -268,7 +268,11 @@ int tcx_f32_to_h2_scaled(const float* x, void* y, size_t n, const unsigned* absm
 
 /* Multi-head self-attention core of SelfAttention2d (sde_score_model.py:150-160):
  * qkv [Bt,N,3C] (1x1-conv output, channel order [q,k,v], head-major inside each),
- * out [Bt,N,C] = softmax(q k^T / sqrt(C/heads)) v. */
+ * out [Bt,N,C] = softmax(q k^T / sqrt(C/heads)) v.
+ * N <= 256 or N % 256 == 0; head dim 8, 16, 24, 32, 48 or 64 (N > 256: 16, 32, 48, 64).
+ * Bounds shared by tcx_attention, tcx_attention_h2 and the three tcx_attention_split* entries: Bt in
+ * [0, 65535] and heads in [1, 65535] (each is a grid row count); outside them the call is refused with
+ * TCX_EINVAL before any launch.  Bt == 0 returns TCX_OK and writes nothing. */
 int tcx_attention(const float* qkv, float* out, int Bt, int N, int C, int heads, void* stream);
 
 /* ------------------------------------------------------------------ score U-Net */

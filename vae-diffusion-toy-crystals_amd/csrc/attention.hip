@@ -432,6 +432,8 @@ extern "C" int tcx_attention(const float* qkv, float* out, int Bt, int N, int C,
     TCX_REQUIRE(qkv && out && heads > 0 && C % heads == 0, "tcx_attention: bad args");
     TCX_REQUIRE(N > 0 && (N <= 4 * MAXK || N % 256 == 0), "tcx_attention: N must be <= 256 or a multiple of 256");
     TCX_REQUIRE(aligned16(qkv) && aligned16(out), "tcx_attention: pointers must be 16-B aligned");
+    TCX_REQUIRE(Bt >= 0 && Bt <= 65535, "tcx_attention: Bt must be in [0, 65535] (one grid row per image)");
+    TCX_REQUIRE(heads <= 65535, "tcx_attention: heads must be in [1, 65535] (one grid row per head)");
     if (Bt == 0) return TCX_OK;
     const int D = C / heads;
     hipStream_t st = (hipStream_t)stream;
@@ -472,6 +474,8 @@ extern "C" int tcx_attention_h2(const float* qkv, void* out, int Bt, int N, int 
     TCX_REQUIRE(N > 0 && ((N <= 256 && N % 32 == 0) || N % 256 == 0),
                 "tcx_attention_h2: needs N %% 32 == 0 and N <= 256, or N %% 256 == 0");
     TCX_REQUIRE(aligned16(qkv) && aligned16(out), "tcx_attention_h2: pointers must be 16-B aligned");
+    TCX_REQUIRE(Bt >= 0 && Bt <= 65535, "tcx_attention_h2: Bt must be in [0, 65535] (one grid row per image)");
+    TCX_REQUIRE(heads <= 65535, "tcx_attention_h2: heads must be in [1, 65535] (one grid row per head)");
     if (Bt == 0) return TCX_OK;
     float* o = (float*)out;
     hipStream_t st = (hipStream_t)stream;

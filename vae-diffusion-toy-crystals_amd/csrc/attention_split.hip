@@ -24,6 +24,7 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
 
 // tile load (global -> registers) and store (registers -> LDS stage, V transposed) of the kernel below
 #define TCX_ATT_LOAD_R(k0, kreg, vreg) \
@@ -247,8 +248,23 @@ __global__ __launch_bounds__(512) void k_attention_split(const char* __restrict_
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
                         const float v = __builtin_amdgcn_exp2f(fmaf(sacc[n][8 * s + e], scale2, mb));
-                        if constexpr (!ONES) lt += v;
                         pb[e] = (__bf16)v;
+                    }
+                    // D = 32, 64 (no ONES row): l sums the ROUNDED p the MFMA multiplies, as the ONES row
+                    // does, so the output stays a convex combination of V rows.  Under the deferred max the
+                    // row's largest p is no longer the exact 2^10, and an unrounded l left its bf16 rounding
+                    // (up to 2^-8) in the output of a peaked row (tests/test_gpu_attn.py, gauss(3)).
+                    // v_dot2c_f32_bf16 against packed ones adds two of the packed p per instruction: half
+                    // the VALU of the fp32 adds it replaces
+                    if constexpr (!ONES) {
+#pragma unroll
+                        for (int e = 0; e < 8; e += 2) {
+                            bf2 pp, one;
+                            pp[0] = pb[e];
+                            pp[1] = pb[e + 1];
+                            one[0] = one[1] = (__bf16)1.0f;
+                            lt = __builtin_amdgcn_fdot2_f32_bf16(pp, one, lt, false);
+                        }
                     }
 #pragma unroll
                     for (int t = 0; t < DT; ++t) {
@@ -389,6 +405,8 @@ int attention_split(const void* qkv, void* out, int Bt, int N, int C, int heads,
     TCX_REQUIRE(qkv && out && heads > 0 && C % heads == 0, "tcx_attention_split: bad args");
     TCX_REQUIRE(N > 0 && N % 256 == 0, "tcx_attention_split: needs N %% 256 == 0");
     TCX_REQUIRE(aligned16(qkv) && aligned16(out), "tcx_attention_split: pointers must be 16-B aligned");
+    TCX_REQUIRE(Bt >= 0 && Bt <= 65535, "tcx_attention_split: Bt must be in [0, 65535] (one grid row per image)");
+    TCX_REQUIRE(heads <= 65535, "tcx_attention_split: heads must be in [1, 65535] (one grid row per head)");
     if (Bt == 0) return TCX_OK;
 #define TCX_ATT_D(D_)                                                                        \
     case D_:                                                                                 \
