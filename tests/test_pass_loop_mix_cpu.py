@@ -3,8 +3,8 @@ assembly (tools/pass_valu_mix.py): the first conv's record kernel, the banded x2
 the register head.  They move 32-48 B per record and were bound by VALU issue, not by HBM: 313 VALU per
 record in k_conv_first_rec's loop, 220 in k_upsample2x_band<4, true>'s, 222 per 8-pixel pass in k_head8r<3>,
 half of it index decode (divisions, integer multiplies, address forming, ds_bpermute shuffles).  Static:
-compiles unet.hip and norm.hip to gfx950 assembly with the Makefile's flags (a minute or two, once per
-session), no GPU.
+compiles unet_first.hip, unet_head.hip and norm.hip to gfx950 assembly with the Makefile's flags (a minute or
+two, once per session), no GPU.
 
 Bounds.  First conv: the arithmetic of a record is about 160 VALU (72 fma, 8 x (fma, mul, exp2, add, rcp,
 mul), ~30 for the f16 split, the range flag); at 183 the modelled VALU time equals the 74 us the 403 MB
@@ -50,7 +50,7 @@ def asm(tmp_path_factory):
     d = tmp_path_factory.mktemp("pass_asm")
     procs = {n: subprocess.Popen([hipcc, *_makefile_flags(), "--cuda-device-only", "-S", n + ".hip", "-o",
                                   str(d / (n + ".s"))], cwd=CSRC, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-             for n in ("unet", "norm")}
+             for n in ("unet_first", "unet_head", "norm")}
     for n, p in procs.items():
         out, _ = p.communicate(timeout=900)
         assert p.returncode == 0, out.decode(errors="replace")[-2000:]
@@ -93,7 +93,7 @@ def test_tool_counts_the_store_loop(tmp_path):
 
 
 def test_first_conv_record_loop(asm):
-    cnt, rsrc, looped = _one(asm["unet"], FIRST)
+    cnt, rsrc, looped = _one(asm["unet_first"], FIRST)
     assert looped and cnt["stores"] == 2  # one record per trip
     assert cnt["imul32"] == 0
     assert rsrc["ScratchSize"] == 0
@@ -112,7 +112,7 @@ def test_upsample_record_loop(asm, sym):
 
 
 def test_head_passes(asm):
-    cnt, rsrc, looped = _one(asm["unet"], HEAD)
+    cnt, rsrc, looped = _one(asm["unet_head"], HEAD)
     assert not looped and cnt["stores"] == 16  # the 8 passes are unrolled: the whole kernel, two stores per pass
     assert cnt["bpermute"] == 0
     assert rsrc["ScratchSize"] == 0

@@ -17,6 +17,7 @@
 // The output is a convex combination of V rows, so |O| <= max|V| < 65504: no range flag.
 #include "common.hpp"
 #include "h2.hpp"
+#include "passes.hpp"
 
 namespace tcx {
 namespace {

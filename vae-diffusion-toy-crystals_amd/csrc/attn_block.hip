@@ -25,6 +25,7 @@
 // |v| >= kH2Max, as the qkv conv's epilogue did).  Phase 2 is k_attention_split<48, 0>'s loop body on the
 // two 128-key tiles, which are both resident (N = 256): no loads, one barrier.
 #include "conv_common.hpp"
+#include "passes.hpp"
 
 namespace tcx {
 namespace {
@@ -325,7 +326,7 @@ __global__ __launch_bounds__(512) void k_attn_block(const char* __restrict__ x, 
 
 }  // namespace
 
-// Shapes the fused kernel takes (unet.hip falls back to the three launches otherwise): f16x3 records,
+// Shapes the fused kernel takes (unet.hip's unet_body falls back to the three launches otherwise): f16x3 records,
 // N = 256 tokens, C = 192 in 4 heads, the qkv weight packed [3C][C] with no K padding, 16-B aligned pointers.
 bool attn_block_ok(int fmt, int Bt, int N, int C, int heads, const tcx_conv& qkv, const tcx_conv& proj, const void* x,
                    const void* a, const void* o) {

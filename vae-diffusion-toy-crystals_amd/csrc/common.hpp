@@ -46,6 +46,17 @@ inline int check_launch(const char* what) {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// Environment switches (A/B measurements).  A use site reads its switch once, into a `static const` of its
+// own, and checks the range itself.  env_on: on unless the value starts with '0'.
+inline bool env_on(const char* name) {
+    const char* e = getenv(name);
+    return !(e && e[0] == '0');
+}
+inline int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

@@ -8,6 +8,7 @@
 #include "common.hpp"
 #include "skinny.hpp"
 #include "h2.hpp"
+#include "passes.hpp"
 
 namespace tcx {
 namespace {
@@ -1216,7 +1217,8 @@ extern "C" int tcx_upsample2x(const float* x, float* y, int Bt, int H, int W, in
 
 namespace tcx {
 // tcx_debug_pass_forms (tests, A/B): a set bit selects the form before the decode-free one on this host thread —
-// bit 0 k_conv_first_rec96, bit 1 the fixed-shape k_upsample2x_band, bit 2 k_head8r's DPP reduction (unet.hip)
+// bit 0 k_conv_first_rec96 (unet_first.hip), bit 1 the fixed-shape k_upsample2x_band, bit 2 k_head8r's DPP reduction
+// (unet_head.hip)
 thread_local int g_pass_forms = 0;
 int pass_forms() { return g_pass_forms; }
 
