@@ -338,6 +338,7 @@ int tcx_set_sample_lanes(int lanes);
  *         3 Heun stage 1: drift d (-> eps_out) and x_e = x + d*dt (-> x2)   (:490-492, :426-449);
  *         4 Heun stage 2: x += 0.5*(d + d(x_e))*dt, d read from eps_out, x_e = x2 (:493);
  *         5 as 2 but stops at x0_hat = (x - s*eps)/max(a,1e-6) (:566): no (x0+1)/2 map, no clamp.
+ *         (6 and 7, the DPM-Solver++ steps, are tcx_dpmpp_sample's own: this entry point refuses them.)
  *   scal: device pointer to the current row of the per-step table.
  *   z: noise [B,H,W] for mode 1 (host-injected, parity mode) or NULL to draw it in-kernel from
  *   Philox4x32-10 keyed by (seed, step) (fast mode).  */
@@ -386,6 +387,34 @@ int tcx_ode_sample_ex(const tcx_unet* net, float* x, const int64_t* y_cat, const
  * tables grow with n_steps and the library no longer allocates them itself. */
 size_t tcx_sde_workspace_size(const tcx_unet* net, int B, int H, int W, int n_steps, float guidance);
 size_t tcx_ode_workspace_size(const tcx_unet* net, int B, int H, int W, int n_steps, float guidance);
+
+/* DPM-Solver++(2M) sampler: the multistep data-prediction solver of Lu, Zhou, Bao, Chen, Li, Zhu,
+ * "DPM-Solver++: Fast Solver for Guided Sampling of Diffusion Probabilistic Models" (2022), Algorithm 2,
+ * on the VP-SDE — second order at ONE U-Net evaluation per step (the reference project has no such
+ * sampler, so there is no reference line to cite).  On the grid t_0 = 1 .. t_n = t_end of scal_table, with
+ * I(t) = beta_min t + (beta_max - beta_min) t^2 / 2, alpha = exp(-I/2), sigma = sqrt(-expm1(-I)),
+ * lambda = ln alpha - ln sigma and h_i = lambda_{i+1} - lambda_i, step i is
+ *   x0_i    = (x_i - sigma_i eps_i) / alpha_i                        (eps_i: the CFG-combined U-Net output)
+ *   D_i     = x0_i                                                   (first-order step)
+ *           = (1 + 1/(2r)) x0_i - (1/(2r)) x0_{i-1},  r = h_{i-1}/h_i  (second-order step)
+ *   x_{i+1} = (sigma_{i+1}/sigma_i) x_i - alpha_{i+1} expm1(-h_i) D_i
+ * and x0_i becomes the history.  Step 0 is first order; every step is when order == 1; with
+ * TCX_DPM_LOWER_ORDER_FINAL step n-1 is too.  After the n steps the final projection of the other two
+ * samplers runs on scal_table row n (n_steps + 1 evaluations in all; n_steps == 0 is the projection alone).
+ *   coef_table [n_steps][TCX_DPM_COEF] on device, row i = {sigma_i, alpha_i, sigma_{i+1}/sigma_i,
+ *   -alpha_{i+1} expm1(-h_i), 1 + 1/(2r), -1/(2r), lambda_i, h_i}: computed on the host in float64 from the
+ *   fp32 grid values of scal_table and rounded once to fp32 (a first-order row holds 1 and 0 for the two D
+ *   coefficients; the kernel reads the first six).
+ *   order: 1 or 2.  flags: TCX_SAMPLE_X0_HAT | TCX_DPM_LOWER_ORDER_FINAL.
+ *   Workspace: tcx_dpmpp_workspace_size bytes (the reverse SDE's parts plus the history image); a smaller
+ *   ws_bytes is TCX_EWS with the required size in the message.  Runs under tcx_set_sample_lanes like the
+ *   other samplers; x_T is the caller's (tcx_randn_at for a shard of a larger batch). */
+#define TCX_DPM_COEF 8
+#define TCX_DPM_LOWER_ORDER_FINAL 2
+size_t tcx_dpmpp_workspace_size(const tcx_unet* net, int B, int H, int W, int n_steps, float guidance);
+int tcx_dpmpp_sample(const tcx_unet* net, float* x, const int64_t* y_cat, const float* y_cont, int B,
+                     int H, int W, int n_steps, int order, float guidance, const float* scal_table,
+                     const float* coef_table, int flags, void* ws, size_t ws_bytes, void* stream);
 
 /* Test hook for the samplers' error paths: the k-th U-Net evaluation after the call (k > 0) fails
  * with TCX_EINVAL before launching anything (one shot; 0 disarms).  Per host thread: arming it never

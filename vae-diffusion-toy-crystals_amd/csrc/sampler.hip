@@ -1,6 +1,7 @@
 // CondUNetTiny's samplers, natively (the reference's models/sde_score_model.py:507-569 reverse SDE, :452-504
-// PF-ODE): the whole loop of a sampling call is one call here.  Host code only: every step is one or two
-// U-Net evaluations (unet.hip) whose last kernel, k_step, applies the sampler update.
+// PF-ODE; DPM-Solver++(2M), which the reference does not have): the whole loop of a sampling call is one call
+// here.  Host code only: every step is one or two U-Net evaluations (unet.hip) whose last kernel, k_step,
+// applies the sampler update.
 #include <map>
 #include <mutex>
 #include <optional>
@@ -86,8 +87,8 @@ thread_local int g_fail_eval = 0;
 
 // Workspace of the samplers (one caller allocation; the library allocates nothing): the U-Net
 // evaluations' workspace for the (CFG-doubled) rows under the current lane setting, then the
-// conditioning tables of the call's n_steps + 1 step-table rows (and for the PF-ODE the drift d and
-// the Euler point x_e between them).
+// conditioning tables of the call's n_steps + 1 step-table rows (and between them, for the PF-ODE the
+// drift d and the Euler point x_e, for DPM-Solver++ the history image).
 size_t sde_ws_parts(const tcx_unet* net, int B, int H, int W, int n_steps, float guidance, size_t* unet_part) {
     const size_t u = align_up(tcx_unet_workspace_size(net, guidance > 0.f ? 2 * B : B, H, W), 256);
     if (unet_part) *unet_part = u;
@@ -99,6 +100,12 @@ size_t ode_ws_parts(const tcx_unet* net, int B, int H, int W, int n_steps, float
     if (img_part) *img_part = im;
     return sde_ws_parts(net, B, H, W, n_steps, guidance, unet_part) + 2 * im;
 }
+size_t dpmpp_ws_parts(const tcx_unet* net, int B, int H, int W, int n_steps, float guidance, size_t* unet_part,
+                      size_t* img_part) {
+    const size_t im = align_up((size_t)B * H * W * sizeof(float), 256);
+    if (img_part) *img_part = im;
+    return sde_ws_parts(net, B, H, W, n_steps, guidance, unet_part) + im;
+}
 
 // One lane's share of a sampling call: images [b0, b1), their element offset e = b0 * H * W, the lane's
 // slice of the U-Net workspace and its stream.
@@ -109,7 +116,7 @@ struct Lane {
     hipStream_t st;
 };
 
-// The step loop of both samplers: body(i, lane) for every step-table row i = 0 .. n_steps (the last: the
+// The step loop of the samplers: body(i, lane) for every step-table row i = 0 .. n_steps (the last: the
 // final projection), step outer and lane inner, so the lanes' enqueues interleave.  L lanes when the lane
 // streams exist and the U-Net workspace [wbase, wbase + ubytes) holds L lane slices, else one lane: the
 // caller's stream and the whole workspace, no event, no wait, no join.  who: the sampler, for error texts.
@@ -282,4 +289,49 @@ extern "C" int tcx_ode_sample(const tcx_unet* net, float* x, const int64_t* y_ca
                               int W, int n_steps, float guidance, const float* scal_table, void* ws, size_t ws_bytes,
                               void* stream) {
     return tcx_ode_sample_ex(net, x, y_cat, y_cont, B, H, W, n_steps, guidance, scal_table, 0, ws, ws_bytes, stream);
+}
+
+extern "C" size_t tcx_dpmpp_workspace_size(const tcx_unet* net, int B, int H, int W, int n_steps, float guidance) {
+    if (!net || B <= 0 || n_steps < 0) return 0;
+    return dpmpp_ws_parts(net, B, H, W, n_steps, guidance, nullptr, nullptr);
+}
+
+// DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2; tcx.h states the update): one evaluation per step, whose k_step
+// applies the first-order (mode 6) or second-order (mode 7) update from the step's coefficient row.
+extern "C" int tcx_dpmpp_sample(const tcx_unet* net, float* x, const int64_t* y_cat, const float* y_cont, int B,
+                                int H, int W, int n_steps, int order, float guidance, const float* scal_table,
+                                const float* coef_table, int flags, void* ws, size_t ws_bytes, void* stream) {
+    TCX_REQUIRE(x && scal_table && n_steps >= 0 && ws, "tcx_dpmpp_sample: bad args");
+    TCX_REQUIRE(order == 1 || order == 2, "tcx_dpmpp_sample: order must be 1 or 2, got %d", order);
+    TCX_REQUIRE((flags & ~(TCX_SAMPLE_X0_HAT | TCX_DPM_LOWER_ORDER_FINAL)) == 0, "tcx_dpmpp_sample: unknown flags %d",
+                flags);
+    TCX_REQUIRE(coef_table || n_steps == 0, "tcx_dpmpp_sample: null coefficient table");
+    TCX_TRY(validate(net, B, H, W));
+    const int fmode = (flags & TCX_SAMPLE_X0_HAT) ? 5 : 2;
+    const bool lower_final = (flags & TCX_DPM_LOWER_ORDER_FINAL) != 0;
+    size_t ubytes = 0, ibytes = 0;
+    const size_t need = dpmpp_ws_parts(net, B, H, W, n_steps, guidance, &ubytes, &ibytes);
+    if (ws_bytes < need) {
+        set_error("tcx_dpmpp_sample: workspace too small (%zu < %zu, tcx_dpmpp_workspace_size)", ws_bytes, need);
+        return TCX_EWS;
+    }
+    char* wbase = reinterpret_cast<char*>(align_up(reinterpret_cast<uintptr_t>(ws), 256));
+    hipStream_t st = (hipStream_t)stream;
+    // [U-Net workspace][history x0][conditioning tables]; a lane takes its images' slice of the history
+    float* hist = reinterpret_cast<float*>(wbase + ubytes);
+    CondMaps cmap;
+    TCX_TRY(make_cond_maps(net, scal_table, n_steps + 1, y_cat, y_cont, B, st, wbase + ubytes + ibytes, cmap));
+    return step_loop("tcx_dpmpp_sample", net, B, H, W, n_steps, guidance, wbase, ubytes, st, [&](int i, const Lane& lane) {
+        const float* row = scal_table + (size_t)i * TCX_SCAL;
+        float* xl = x + lane.e;
+        EvalArgs a = lane_eval(net, y_cat, y_cont, H, W, guidance, lane);
+        a.x = xl; a.t = row; a.scal = row; a.e_base = lane.e; a.ct = cmap.at(i, lane.b0);
+        if (i < n_steps) {  // one multistep update of x, first order where the history is not to be used
+            const bool first = order == 1 || i == 0 || (lower_final && i == n_steps - 1);
+            a.mode = first ? 6 : 7; a.x_inout = xl; a.coef = coef_table + (size_t)i * TCX_DPM_COEF; a.hist = hist + lane.e;
+        } else {  // final projection -> image written over x
+            a.mode = fmode; a.eps_out = xl;
+        }
+        return unet_eval_impl(a);
+    });
 }

@@ -361,10 +361,11 @@ int unet_eval_impl(const EvalArgs& e) {
     TCX_TRY(validate(net, B, H, W));
     TCX_TRY(injected_failure());
     TCX_REQUIRE(e.x && e.t && e.y_cat && e.y_cont && e.ws, "tcx_unet_eval: null pointer");
-    TCX_REQUIRE(mode >= 0 && mode <= 5, "tcx_unet_eval: bad mode");
+    TCX_REQUIRE(mode >= 0 && mode <= 7, "tcx_unet_eval: bad mode");
     TCX_REQUIRE(mode == 0 || e.scal, "tcx_unet_eval: sampler modes need the step table row");
-    TCX_REQUIRE(mode == 1 || e.eps_out, "tcx_unet_eval: eps_out needed");
-    TCX_REQUIRE((mode != 1 && mode != 3 && mode != 4) || e.x_inout, "tcx_unet_eval: x_inout needed");
+    TCX_REQUIRE(mode == 1 || mode >= 6 || e.eps_out, "tcx_unet_eval: eps_out needed");
+    TCX_REQUIRE((mode != 1 && mode != 3 && mode != 4 && mode < 6) || e.x_inout, "tcx_unet_eval: x_inout needed");
+    TCX_REQUIRE(mode < 6 || (e.coef && e.hist), "tcx_unet_eval: DPM-Solver++ steps need the coefficient row and history");
     TCX_REQUIRE(mode != 3 || e.x2, "tcx_unet_eval: Heun stage 1 needs x2");
     const int cfg = e.guidance > 0.f ? 1 : 0;
     const int Bc = chunk_images(B, max_pass_rows(net, H, W) / (cfg ? 2 : 1));
@@ -389,6 +390,7 @@ int unet_eval_impl(const EvalArgs& e) {
         a.x2 = e.x2 ? e.x2 + e0 : nullptr; a.eps_out = e.eps_out ? e.eps_out + e0 : nullptr;
         a.z = e.z ? e.z + e0 : nullptr;
         a.seed = e.seed; a.step = e.step; a.e0 = e.e_base + e0;
+        a.coef = e.coef; a.hist = e.hist ? e.hist + e0 : nullptr;
         TCX_TRY(launch_step(a, e.stream));
     }
     return TCX_OK;
@@ -409,6 +411,8 @@ extern "C" int tcx_unet_eval(const tcx_unet* net, const float* x, float* x2, con
                              const int64_t* y_cat, const float* y_cont, int B, int H, int W, float guidance, int mode,
                              const float* scal, const float* z, uint64_t seed, uint64_t step, float* x_inout,
                              float* eps_out, void* ws, size_t ws_bytes, void* stream) {
+    // modes 6 / 7 (the DPM-Solver++ steps) exist only inside tcx_dpmpp_sample
+    TCX_REQUIRE(mode >= 0 && mode <= 5, "tcx_unet_eval: bad mode");
     EvalArgs a{};
     a.net = net; a.x = x; a.x2 = x2; a.t = t; a.t_per_sample = t_per_sample; a.y_cat = y_cat; a.y_cont = y_cont;
     a.B = B; a.H = H; a.W = W; a.guidance = guidance; a.mode = mode; a.scal = scal; a.z = z; a.seed = seed; a.step = step;

@@ -31,6 +31,8 @@ struct StepFields {
     const float* z;
     uint64_t seed, step;
     size_t e0;  // element offset of this batch chunk (Philox counter = e0 + i: chunking-invariant noise)
+    const float* coef;    // DPM-Solver++ (modes 6 / 7): current row of the coefficient table [TCX_DPM_COEF]
+    float* hist;          // DPM-Solver++: the previous step's data prediction x0 [B][HW]
 };
 
 namespace {
@@ -83,8 +85,8 @@ struct H2Ctx {
 // one piece), and the evaluation's rows of the sampler's conditioning table (none: k_cond runs).
 struct EvalArgs {
     const tcx_unet* net;
-    const float *x, *t, *y_cont, *scal, *z;
-    float *x2, *x_inout, *eps_out;
+    const float *x, *t, *y_cont, *scal, *z, *coef;
+    float *x2, *x_inout, *eps_out, *hist;
     const int64_t* y_cat;
     int t_per_sample, B, H, W, mode;
     float guidance;

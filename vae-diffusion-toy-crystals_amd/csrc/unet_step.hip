@@ -1,8 +1,9 @@
 // Philox4x32-10 noise and the sampler step of CondUNetTiny's samplers (the reference's sde_score_model.py:507-569
 // reverse SDE, :452-504 PF-ODE):
 //   k_step — the out conv's 9-tap circular gather of the head partials r + bias, the CFG combine
-//            eps_u + s (eps_c - eps_u), and the sampler update (EM / Heun stage / final x0 projection) in one pass;
-//            noise either host-injected or Philox in-kernel.
+//            eps_u + s (eps_c - eps_u), and the sampler update (EM / Heun stage / final x0 projection, or a
+//            DPM-Solver++(2M) step, which the reference does not have) in one pass; noise either host-injected
+//            or Philox in-kernel.
 #include "unet.hpp"
 
 namespace tcx {
@@ -95,6 +96,15 @@ __global__ __launch_bounds__(256) void k_step(StepArgs a) {
             const float d = ((-0.5f * beta) * xv) - ((0.5f * beta) * score);
             a.eps_out[i] = d;
             a.x2[i] = xv + d * dt;
+        } else if (a.mode >= 6) {
+            // DPM-Solver++(2M) step (Lu et al. 2022, Algorithm 2; tcx.h: tcx_dpmpp_sample): mode 6 first order
+            // (writes the history), mode 7 second order (reads and rewrites it)
+            const float sigma = a.coef[0], alpha = a.coef[1], cx = a.coef[2], cd = a.coef[3];
+            const float xv = a.x_inout[i];
+            const float x0 = (xv - sigma * eps) / alpha;
+            const float D = a.mode == 7 ? (a.coef[4] * x0) + (a.coef[5] * a.hist[i]) : x0;
+            a.hist[i] = x0;
+            a.x_inout[i] = (cx * xv) + (cd * D);
         } else {
             // Heun stage 2 at t_next on x_e: x += 0.5 (d + d_next) dt  (sde_score_model.py:492-493)
             const float dt = a.scal[2];

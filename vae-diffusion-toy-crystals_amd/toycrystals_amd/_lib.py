@@ -25,6 +25,8 @@ c_ll = ctypes.c_longlong
 
 TCX_SCAL = 8
 TCX_SAMPLE_X0_HAT = 1  # tcx_{sde,ode}_sample_ex flag: return the unclamped x0_hat
+TCX_DPM_COEF = 8  # floats per row of tcx_dpmpp_sample's coefficient table
+TCX_DPM_LOWER_ORDER_FINAL = 2  # tcx_dpmpp_sample flag: the last step is first order
 
 
 class TcxConv(ctypes.Structure):
@@ -139,6 +141,9 @@ _SIGS = {
                                   c_fp, c_int, c_fp, c_size, c_fp]),
     "tcx_sde_sample_shard": (c_int, [ctypes.POINTER(TcxUnet), c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_float,
                                      c_fp, c_fp, c_u64, c_int, c_u64, c_fp, c_size, c_fp]),
+    "tcx_dpmpp_workspace_size": (c_size, [ctypes.POINTER(TcxUnet), c_int, c_int, c_int, c_int, c_float]),
+    "tcx_dpmpp_sample": (c_int, [ctypes.POINTER(TcxUnet), c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int,
+                                 c_float, c_fp, c_fp, c_int, c_fp, c_size, c_fp]),
     "tcx_randn": (c_int, [c_fp, c_size, c_u64, c_u64, c_fp]),
     "tcx_randn_at": (c_int, [c_fp, c_size, c_u64, c_u64, c_u64, c_fp]),
     "tcx_linear": (c_int, [c_fp, c_int, c_fp, c_int, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_fp]),

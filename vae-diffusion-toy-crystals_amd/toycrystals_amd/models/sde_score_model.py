@@ -12,6 +12,8 @@ Reference map:
   SelfAttention2d :114-167, CondUNetTiny :170-266, VPSDE :273-298, save_sde_samples :301-355,
   diffusion_loss_eps :358-399, predict_eps_cfg :402-423, _probflow_drift :426-449,
   sample_probability_flow_ode :452-504, sample_reverse_sde_euler_maruyama :507-569.
+Beyond the reference: sample_dpm_solver_pp / dpmpp_table, the DPM-Solver++(2M) multistep sampler
+(Lu et al. 2022, Algorithm 2), second order at one U-Net evaluation per step.
 """
 from __future__ import annotations
 
@@ -26,8 +28,8 @@ import torch.nn as nn
 
 from .. import _lib
 from .. import functional as TF
-from .._lib import (_CONV_NAMES, TCX_SAMPLE_X0_HAT, TCX_SCAL, TcxConv, TcxUnet, check, lib, ptr,
-                    require_gpu_tensor, stream_ptr)
+from .._lib import (_CONV_NAMES, TCX_DPM_COEF, TCX_DPM_LOWER_ORDER_FINAL, TCX_SAMPLE_X0_HAT, TCX_SCAL, TcxConv,
+                    TcxUnet, check, lib, ptr, require_gpu_tensor, stream_ptr)
 
 
 # =========================
@@ -449,11 +451,46 @@ def step_table(sde: VPSDE, n_steps: int, t_end: float) -> torch.Tensor:
     return tab.contiguous()
 
 
+def dpmpp_table(sde: VPSDE, n_steps: int, t_end: float, order: int = 2,
+                lower_order_final: bool = True) -> torch.Tensor:
+    """Per-step coefficients [n_steps, TCX_DPM_COEF] of DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2;
+    include/tcx.h states the update) on `step_table`'s grid: row i = {sigma_i, alpha_i,
+    sigma_{i+1}/sigma_i, -alpha_{i+1} expm1(-h_i), 1 + 1/(2r), -1/(2r), lambda_i, h_i} with
+    I(t) = beta_min t + (beta_max - beta_min) t^2 / 2, alpha = exp(-I/2), sigma = sqrt(-expm1(-I)),
+    lambda = ln alpha - ln sigma, h_i = lambda_{i+1} - lambda_i and r = h_{i-1}/h_i.  Computed in
+    float64 from the fp32 grid values (the t the U-Net sees) and rounded once to fp32.  A first-order
+    step (step 0; every step at order 1; step n-1 under lower_order_final) holds 1 and 0 for the
+    two history coefficients."""
+    if order not in (1, 2):
+        raise ValueError(f"order must be 1 or 2, got {order}")
+    n = int(n_steps)
+    ts = step_table(sde, n, t_end)[:, 0].to(torch.float64)
+    I = sde.beta_min * ts + 0.5 * (sde.beta_max - sde.beta_min) * ts ** 2
+    alpha = torch.exp(-0.5 * I)
+    sigma = torch.sqrt(-torch.expm1(-I))
+    lam = -0.5 * I - torch.log(sigma)
+    h = lam[1:] - lam[:-1]
+    tab = torch.zeros((n, TCX_DPM_COEF), dtype=torch.float64)
+    if n > 0:
+        tab[:, 0], tab[:, 1] = sigma[:-1], alpha[:-1]
+        tab[:, 2] = sigma[1:] / sigma[:-1]
+        tab[:, 3] = -alpha[1:] * torch.expm1(-h)
+        tab[:, 4] = 1.0
+        tab[:, 6], tab[:, 7] = lam[:-1], h
+    for i in range(1, n):
+        if order == 2 and not (lower_order_final and i == n - 1):
+            r = h[i - 1] / h[i]
+            tab[i, 4], tab[i, 5] = 1.0 + 1.0 / (2.0 * r), -1.0 / (2.0 * r)
+    return tab.to(torch.float32).contiguous()
+
+
 @torch.no_grad()
 def save_sde_samples(model: CondUNetTiny, sde: VPSDE, out_path: str, device: torch.device, n: int = 36,
                      theta_max: float = math.pi / 3.0, steps: int = 200, cfg: float = 0.0, t_end: float = 1e-3,
-                     sampler: str = "ode") -> None:
-    """Save a 6x6 grid: cycle lattice types, sweep theta in [0, pi/3] (sde_score_model.py:301-355)."""
+                     sampler: str = "ode", *, dpmpp: Optional[dict] = None) -> None:
+    """Save a 6x6 grid: cycle lattice types, sweep theta in [0, pi/3] (sde_score_model.py:301-355).
+    sampler="dpmpp" (not in the reference) is sample_dpm_solver_pp; `dpmpp` holds its own keywords
+    (order, lower_order_final)."""
     import matplotlib
     matplotlib.use("Agg")
     import matplotlib.pyplot as plt
@@ -469,8 +506,10 @@ def save_sde_samples(model: CondUNetTiny, sde: VPSDE, out_path: str, device: tor
         x = sample_probability_flow_ode(**kw)
     elif sampler == "sde":
         x = sample_reverse_sde_euler_maruyama(**kw)
+    elif sampler == "dpmpp":
+        x = sample_dpm_solver_pp(**kw, **(dpmpp or {}))
     else:
-        raise ValueError(f"Unknown sampler='{sampler}'. Use 'ode' or 'sde'.")
+        raise ValueError(f"Unknown sampler='{sampler}'. Use 'ode', 'sde' or 'dpmpp'.")
     fig, axes = plt.subplots(6, 6, figsize=(6, 6))
     fig.suptitle(f"{sampler} | steps={steps} | cfg={cfg:.2f} | t_end={t_end:g}", fontsize=10)
     for i, ax in enumerate(axes.flat):
@@ -642,5 +681,48 @@ def sample_probability_flow_ode(model: CondUNetTiny, sde: VPSDE, y_cat: torch.Te
         check(L.tcx_ode_sample_ex(ctypes.byref(pk.net), ptr(x), ptr(y_cat), ptr(y_cont), B, H, W, int(n_steps), g,
                                   ptr(tab), TCX_SAMPLE_X0_HAT if return_x0_hat else 0, ptr(ws), nbytes, st),
               "tcx_ode_sample")
+    pk.run(H, W, launch)
+    return x
+
+
+@torch.no_grad()
+def sample_dpm_solver_pp(model: CondUNetTiny, sde: VPSDE, y_cat: torch.Tensor, y_cont: torch.Tensor,
+                         img_shape: Tuple[int, int, int, int], n_steps: int = 20,
+                         guidance_scale: float = 0.0, t_end: float = 1e-3, *,
+                         order: int = 2, lower_order_final: bool = True,
+                         x_init: Optional[torch.Tensor] = None,
+                         seed: Optional[int] = None,
+                         return_x0_hat: bool = False,
+                         elem_offset: int = 0) -> torch.Tensor:
+    """DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2), t: 1 -> t_end on the samplers' quadratic grid:
+    the multistep data-prediction solver, second order at ONE U-Net evaluation per step (the Heun
+    PF-ODE sampler takes two), n_steps + 1 evaluations with the final projection.  Not in the
+    reference; the whole loop runs natively (tcx_dpmpp_sample), the update fused into the head's last
+    kernel.  `order=1` is the first-order (DDIM-like) solver; `lower_order_final` makes the last step
+    first order.  x_T, `return_x0_hat` and `elem_offset` as for sample_probability_flow_ode."""
+    if order not in (1, 2):
+        raise ValueError(f"order must be 1 or 2, got {order}")
+    device, B, H, W, t_end, y_cat, y_cont = _sampler_prologue(model, y_cat, y_cont, img_shape, t_end)
+    pk = model.tcx_pack(device)
+    tab = step_table(sde, n_steps, t_end).to(device)
+    coef = dpmpp_table(sde, n_steps, t_end, order, lower_order_final).to(device)
+    L = lib()
+    st = stream_ptr(device)
+    x = torch.empty((B, 1, H, W), device=device, dtype=torch.float32)
+    if x_init is None and seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    g = float(guidance_scale) if guidance_scale > 0.0 else 0.0
+    ws, nbytes = pk.workspace(2 * B if g > 0 else B, H, W,
+                              need=int(L.tcx_dpmpp_workspace_size(ctypes.byref(pk.net), B, H, W, int(n_steps), g)))
+    flags = (TCX_SAMPLE_X0_HAT if return_x0_hat else 0) | (TCX_DPM_LOWER_ORDER_FINAL if lower_order_final else 0)
+
+    def launch():
+        if x_init is not None:
+            x.copy_(x_init.to(device=device, dtype=torch.float32).view_as(x))
+        else:
+            check(L.tcx_randn_at(ptr(x), x.numel(), seed, 0, int(elem_offset), st), "tcx_randn")
+        check(L.tcx_dpmpp_sample(ctypes.byref(pk.net), ptr(x), ptr(y_cat), ptr(y_cont), B, H, W, int(n_steps),
+                                 int(order), g, ptr(tab), ptr(coef) if int(n_steps) > 0 else None, flags, ptr(ws),
+                                 nbytes, st), "tcx_dpmpp_sample")
     pk.run(H, W, launch)
     return x
