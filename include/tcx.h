@@ -636,6 +636,21 @@ int tcx_colsum(const float* x, int Bt, int HW, int C, float* per_batch, float* t
 int tcx_softmax_rows(const float* S, float* P, long long rows, int n, void* stream);
 int tcx_softmax_bwd_rows(const float* P, const float* dP, float* dS, long long rows, int n, void* stream);
 
+/* tcx_attention (fp32, same products, `out` bit-identical to it) that also writes
+ * lse [Bt][heads][N] = ln sum_j exp(scale * q_i.k_j)  (natural log, scale = 1/sqrt(C/heads)).
+ * Shapes: (N <= 256 and N % 32 == 0) or N % 256 == 0; head dim 8,16,24,32,48,64 (N > 256: 16,32,48,64)
+ * — the shapes k_attention_mfma / k_attention_flash serve.  Anything else: TCX_EUNSUP before any launch. */
+int tcx_attention_fwd_lse(const float* qkv, float* out, float* lse, int Bt, int N, int C, int heads, void* stream);
+
+/* Backward of the above without any N x N tensor: dqkv [Bt,N,3C] (every element written) from qkv, out, dout [Bt,N,C] and lse.
+ * ws: tcx_attention_bwd_workspace bytes (delta[b][h][i] = sum_d dout*out); smaller is TCX_EWS with
+ * the size in the message.  Same shape set and the same Bt / heads bounds as tcx_attention; Bt == 0 with a
+ * shape of the set returns TCX_OK and writes nothing (both entries check the shape first).
+ * tcx_attention_bwd_workspace returns 0 for a shape outside the set: callers use it as the predicate. */
+size_t tcx_attention_bwd_workspace(int Bt, int N, int C, int heads);
+int tcx_attention_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv,
+                      int Bt, int N, int C, int heads, void* ws, size_t ws_bytes, void* stream);
+
 /* Elementwise activation (1 ReLU, 2 Sigmoid, 3 SiLU) and its backward from the pre-activation. */
 int tcx_act_fwd(const float* z, float* y, size_t n, int act, void* stream);
 int tcx_act_bwd(const float* z, const float* dy, float* dz, size_t n, int act, void* stream);

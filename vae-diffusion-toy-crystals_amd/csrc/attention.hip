@@ -22,9 +22,10 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 //   O^T = V^T P^T: the probability accumulators ARE the B operands (key = (r&3)+8(r>>2)+4h of
 //                 tile n, query on the lane), A = V^T read from LDS with the same key order.
 // ---------------------------------------------------------------------------------------------
-template <int D>
+template <int D, bool LSE = false>
 __global__ __launch_bounds__(512) void k_attention_mfma(const float* __restrict__ qkv, float* __restrict__ out, int N,
-                                                        int C, float scale, int out_h2, unsigned* ovf) {
+                                                        int C, float scale, int out_h2, unsigned* ovf,
+                                                        float* __restrict__ lse) {
     constexpr int HD = D / 2;           // d per lane half
     constexpr int KS = D + 4;           // K row stride in LDS ((D+4)/4 odd: conflict-free b128)
     constexpr int DT = (D + 31) / 32;   // 32-row tiles of O^T
@@ -118,6 +119,8 @@ __global__ __launch_bounds__(512) void k_attention_mfma(const float* __restrict_
                     oacc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(vr[t * 32], sacc[n][r], oacc[t], 0, 0, 0);
             }
         }
+    // training forward: ln sum_j exp(scale s_j) of the row, all the recomputing backward keeps of P
+    if (LSE && lh == 0) lse[((size_t)b * gridDim.x + h) * N + q] = m * scale + logf(l);
     const float inv = 1.f / l;
     if (out_h2) {  // h2 split record of the query's pixel (h2.hpp): 4 consecutive d per register quad
         bool bad = false;
@@ -153,9 +156,10 @@ __global__ __launch_bounds__(512) void k_attention_mfma(const float* __restrict_
 // exp((m_old - m_new) * scale) when a tile raises the max.  Same fp32 MFMA products as
 // k_attention_mfma; exact softmax up to the rescaling roundings.
 // ---------------------------------------------------------------------------------------------
-template <int D>
+template <int D, bool LSE = false>
 __global__ __launch_bounds__(512) void k_attention_flash(const float* __restrict__ qkv, float* __restrict__ out, int N,
-                                                         int C, float scale, int out_h2, unsigned* ovf) {
+                                                         int C, float scale, int out_h2, unsigned* ovf,
+                                                         float* __restrict__ lse) {
     constexpr int HD = D / 2;
     constexpr int KS = D + 4;
     constexpr int DT = (D + 31) / 32;
@@ -250,6 +254,7 @@ __global__ __launch_bounds__(512) void k_attention_flash(const float* __restrict
                     oacc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(vr[t * 32], sacc[n][r], oacc[t], 0, 0, 0);
             }
     }
+    if (LSE && lh == 0) lse[((size_t)b * gridDim.y + h) * N + q] = m * scale + logf(l);
     const float inv = 1.f / l;
     if (out_h2) {
         bool bad = false;
@@ -278,31 +283,33 @@ __global__ __launch_bounds__(512) void k_attention_flash(const float* __restrict
         }
 }
 
-template <int D>
+// LSE: the training forward (tcx_attention_fwd_lse), which also stores the row log-sum-exp
+template <int D, bool LSE = false>
 int launch_attn_flash(const float* qkv, float* out, int Bt, int N, int C, int heads, hipStream_t st, int out_h2,
-                      unsigned* ovf) {
+                      unsigned* ovf, float* lse = nullptr) {
     const float scale = (float)(1.0 / std::sqrt((double)D));
-    hipLaunchKernelGGL((k_attention_flash<D>), dim3(N / 256, heads, Bt), dim3(512), 0, st, qkv, out, N, C, scale,
-                       out_h2, ovf);
+    hipLaunchKernelGGL((k_attention_flash<D, LSE>), dim3(N / 256, heads, Bt), dim3(512), 0, st, qkv, out, N, C, scale,
+                       out_h2, ovf, lse);
     return check_launch("tcx_attention(flash)");
 }
 
-template <int D>
+template <int D, bool LSE = false>
 int launch_attn_mfma(const float* qkv, float* out, int Bt, int N, int C, int heads, hipStream_t st, int out_h2 = 0,
-                     unsigned* ovf = nullptr) {
+                     unsigned* ovf = nullptr, float* lse = nullptr) {
     const float scale = (float)(1.0 / std::sqrt((double)D));
     constexpr int KS = D + 4, VS = ((D + 31) / 32) * 32;
     const size_t shm = (size_t)N * (KS + VS) * sizeof(float);
     static bool attr_set = false;
     if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attention_mfma<D>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attention_mfma<D, LSE>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
             set_error("tcx_attention: cannot enable 160 KB dynamic LDS");
             return TCX_EHIP;
         }
         attr_set = true;
     }
-    hipLaunchKernelGGL((k_attention_mfma<D>), dim3(heads, Bt), dim3(2 * N), shm, st, qkv, out, N, C, scale, out_h2, ovf);
+    hipLaunchKernelGGL((k_attention_mfma<D, LSE>), dim3(heads, Bt), dim3(2 * N), shm, st, qkv, out, N, C, scale, out_h2,
+                       ovf, lse);
     return check_launch("tcx_attention(mfma)");
 }
 
@@ -466,6 +473,42 @@ extern "C" int tcx_attention(const float* qkv, float* out, int Bt, int N, int C,
         case 64: return launch_attn<64>(qkv, out, Bt, N, C, heads, st);
         default: set_error("tcx_attention: head dim %d unsupported", D); return TCX_EUNSUP;
     }
+}
+
+extern "C" int tcx_attention_fwd_lse(const float* qkv, float* out, float* lse, int Bt, int N, int C, int heads,
+                                     void* stream) {
+    TCX_REQUIRE(qkv && out && lse && heads > 0 && C > 0 && C % heads == 0, "tcx_attention_fwd_lse: bad args");
+    TCX_REQUIRE(aligned16(qkv) && aligned16(out), "tcx_attention_fwd_lse: pointers must be 16-B aligned");
+    TCX_REQUIRE(Bt >= 0 && Bt <= 65535, "tcx_attention_fwd_lse: Bt must be in [0, 65535] (one grid row per image)");
+    TCX_REQUIRE(heads <= 65535, "tcx_attention_fwd_lse: heads must be in [1, 65535] (one grid row per head)");
+    const int D = C / heads;
+    if (!attn_train_shape_ok(N, D)) {
+        set_error("tcx_attention_fwd_lse: N = %d, head dim %d unsupported (N %% 32 == 0 and N <= 256, or N %% 256 == 0; "
+                  "head dim 8, 16, 24, 32, 48 or 64, above N = 256: 16, 32, 48, 64)", N, D);
+        return TCX_EUNSUP;
+    }
+    if (Bt == 0) return TCX_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (N > 256) {
+        switch (D) {
+            case 16: return launch_attn_flash<16, true>(qkv, out, Bt, N, C, heads, st, 0, nullptr, lse);
+            case 32: return launch_attn_flash<32, true>(qkv, out, Bt, N, C, heads, st, 0, nullptr, lse);
+            case 48: return launch_attn_flash<48, true>(qkv, out, Bt, N, C, heads, st, 0, nullptr, lse);
+            case 64: return launch_attn_flash<64, true>(qkv, out, Bt, N, C, heads, st, 0, nullptr, lse);
+            default: break;
+        }
+    } else {
+        switch (D) {
+            case 8: return launch_attn_mfma<8, true>(qkv, out, Bt, N, C, heads, st, 0, nullptr, lse);
+            case 16: return launch_attn_mfma<16, true>(qkv, out, Bt, N, C, heads, st, 0, nullptr, lse);
+            case 24: return launch_attn_mfma<24, true>(qkv, out, Bt, N, C, heads, st, 0, nullptr, lse);
+            case 32: return launch_attn_mfma<32, true>(qkv, out, Bt, N, C, heads, st, 0, nullptr, lse);
+            case 48: return launch_attn_mfma<48, true>(qkv, out, Bt, N, C, heads, st, 0, nullptr, lse);
+            case 64: return launch_attn_mfma<64, true>(qkv, out, Bt, N, C, heads, st, 0, nullptr, lse);
+            default: break;
+        }
+    }
+    return TCX_EUNSUP;  // not reached: attn_train_shape_ok covers both switches
 }
 
 extern "C" int tcx_attention_h2(const float* qkv, void* out, int Bt, int N, int C, int heads, unsigned* ovf,

@@ -57,6 +57,13 @@ inline int env_int(const char* name, int dflt) {
     return e ? atoi(e) : dflt;
 }
 
+// The shapes of the fused training attention (tcx_attention_fwd_lse, tcx_attention_bwd): those
+// k_attention_mfma (N % 32 == 0 up to 256) and k_attention_flash (N % 256 == 0 above) serve; D = head dim.
+inline bool attn_train_shape_ok(int N, int D) {
+    if (N <= 0 || !((N <= 256 && N % 32 == 0) || N % 256 == 0)) return false;
+    return D == 16 || D == 32 || D == 48 || D == 64 || (N <= 256 && (D == 8 || D == 24));
+}
+
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

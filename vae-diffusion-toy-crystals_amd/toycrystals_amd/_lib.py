@@ -185,6 +185,9 @@ _SIGS = {
     "tcx_colsum": (c_int, [c_fp, c_int, c_int, c_int, c_fp, c_fp, c_float, c_fp, c_size, c_fp]),
     "tcx_softmax_rows": (c_int, [c_fp, c_fp, c_ll, c_int, c_fp]),
     "tcx_softmax_bwd_rows": (c_int, [c_fp, c_fp, c_fp, c_ll, c_int, c_fp]),
+    "tcx_attention_fwd_lse": (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
+    "tcx_attention_bwd_workspace": (c_size, [c_int, c_int, c_int, c_int]),
+    "tcx_attention_bwd": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_size, c_fp]),
     "tcx_act_fwd": (c_int, [c_fp, c_fp, c_size, c_int, c_fp]),
     "tcx_act_bwd": (c_int, [c_fp, c_fp, c_fp, c_size, c_int, c_fp]),
     "tcx_mse_loss": (c_int, [c_fp, c_fp, c_size, c_fp, c_fp, c_size, c_fp]),

@@ -512,6 +512,18 @@ class Upsample2xFn(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------- attention
+# Fused training attention (csrc/attention_bwd.hip): the forward keeps only the row log-sum-exp and the
+# backward recomputes P tile by tile, so no [B, heads, N, N] tensor exists (the GEMM chain below passes
+# four of them through HBM per step).  TCX_ATTN_FUSED=0 keeps the chain for every shape (A/B).
+_ATTN_FUSED = os.environ.get("TCX_ATTN_FUSED", "1") != "0"
+
+
+def _attn_fused_ok(N: int, C: int, heads: int) -> bool:
+    """the shapes tcx_attention_fwd_lse / tcx_attention_bwd serve (the library's own predicate: a workspace
+    size of 0 means outside the set); any other runs the GEMM chain"""
+    return _ATTN_FUSED and lib().tcx_attention_bwd_workspace(1, N, C, heads) > 0
+
+
 class AttentionFn(torch.autograd.Function):
     """SDPA over qkv [B, N, 3C] (q | k | v channel blocks, head h = channels h*d..h*d+d) -> [B, N, C]."""
 
@@ -522,6 +534,14 @@ class AttentionFn(torch.autograd.Function):
         B, N, C3 = qkv.shape
         C = C3 // 3
         d = C // heads
+        ctx.heads = heads
+        ctx.fused = _attn_fused_ok(N, C, heads)
+        if ctx.fused:
+            out, lse = _empty((B, N, C), qkv), _empty((B, heads, N), qkv)
+            check(L.tcx_attention_fwd_lse(ptr(qkv), ptr(out), ptr(lse), B, N, C, heads, _st(qkv)),
+                  "tcx_attention_fwd_lse")
+            ctx.save_for_backward(qkv, out, lse)
+            return out
         scale = 1.0 / math.sqrt(d)
         S = _empty((B, heads, N, N), qkv)
         gemm(N, N, d, qkv, C3, 1, qkv, 1, C3, S, N, 1, alpha=scale, batch=B * heads, bdiv=heads,
@@ -532,15 +552,23 @@ class AttentionFn(torch.autograd.Function):
         gemm(N, d, N, P, N, 1, qkv, C3, 1, out, C, 1, batch=B * heads, bdiv=heads,
              a_hl=(heads * N * N, N * N), b_hl=(N * C3, d), c_hl=(N * C, d), b_off=2 * C)
         ctx.save_for_backward(qkv, P)
-        ctx.heads = heads
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        qkv, P = ctx.saved_tensors
         heads = ctx.heads
         dout = dout.contiguous()
         L = lib()
+        if ctx.fused:
+            qkv, out, lse = ctx.saved_tensors
+            B, N, C3 = qkv.shape
+            nb = int(L.tcx_attention_bwd_workspace(B, N, C3 // 3, heads))
+            ws = _ws(qkv.device, nb)
+            dqkv = torch.empty_like(qkv)
+            check(L.tcx_attention_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), B, N, C3 // 3, heads,
+                                      ptr(ws), ws.numel(), _st(qkv)), "tcx_attention_bwd")
+            return dqkv, None
+        qkv, P = ctx.saved_tensors
         B, N, C3 = qkv.shape
         C = C3 // 3
         d = C // heads
