@@ -274,6 +274,13 @@ int tcx_f32_to_h2_scaled(const float* x, void* y, size_t n, const unsigned* absm
  * [0, 65535] and heads in [1, 65535] (each is a grid row count); outside them the call is refused with
  * TCX_EINVAL before any launch.  Bt == 0 returns TCX_OK and writes nothing. */
 int tcx_attention(const float* qkv, float* out, int Bt, int N, int C, int heads, void* stream);
+/* tcx_attention / tcx_attention_h2 for every token count: any N >= 1 (k_attention_ragged, key-tiled
+ * fp32 MFMA with a masked last tile).  out_h2 = 0: out is fp32, ovf ignored; 1: out is h2 records
+ * (C % 8 == 0), ovf as in tcx_attention_h2.  Head dim 8, 16, 24, 32, 48 or 64.  Same Bt / heads bounds;
+ * Bt == 0 returns TCX_OK and writes nothing.  The score U-Net evaluator runs its bottleneck here when
+ * (H/4)*(W/4) is above 256 and no multiple of 256 (96x96: 576 tokens). */
+int tcx_attention_ragged(const float* qkv, void* out, int out_h2, int Bt, int N, int C, int heads,
+                         unsigned* ovf, void* stream);
 
 /* ------------------------------------------------------------------ score U-Net */
 
@@ -304,10 +311,13 @@ typedef struct tcx_unet {
     /* GroupNorm affine, in forward order: down1 x2, down2 x2, mid x2, attn, up2 x2, up1 x2 */
     const float* gn_w[11];
     const float* gn_b[11];
-    /* 0: fp32 MFMA convs; 1: f16x3 split convs over h2 activations (needs base_ch % 32 == 0 and
-     * every conv's wh/wscale); h2_ovf: device word raised when an activation leaves the f16 range
-     * (the host re-runs the evaluation in fp32); 2: bf16 single-product convs and attention over bf16
-     * records (wh/whf/wscale then hold the tcx_pack_conv_weight_bf16 packs; (H/4)*(W/4) % 256 == 0) */
+    /* 0: fp32 MFMA convs, any H, W that are multiples of 4 (>= 8); 1: f16x3 split convs over h2
+     * activations (needs base_ch % 32 == 0, (H/4)*(W/4) % 32 == 0 and every conv's wh/wscale); h2_ovf:
+     * device word raised when an activation leaves the f16 range (the host re-runs the evaluation in
+     * fp32); 2: bf16 single-product convs and attention over bf16 records (wh/whf/wscale then hold the
+     * tcx_pack_conv_weight_bf16 packs; (H/4)*(W/4) % 256 == 0).  The bottleneck attention of N =
+     * (H/4)*(W/4) tokens: N <= 256 or N % 256 == 0 on the kernels of tcx_attention / _h2 / _split, any
+     * other N (precision 0 and 1) on fp32 MFMA by tcx_attention_ragged. */
     int precision;
     unsigned* h2_ovf;
 } tcx_unet;
@@ -328,6 +338,7 @@ int tcx_set_sample_lanes(int lanes);
 #define TCX_SCAL 8
 
 /* One U-Net evaluation of a (possibly CFG-doubled) batch, ending in the fused head.
+ *   H, W: any multiples of 4, at least 8 (the precision field of tcx_unet states what each precision adds).
  *   x [B,H,W] (C=1), t_tab: per-sample t is t_tab[0] (a scalar on device) if t_per_sample==0,
  *   else t [B] (t_tab points at it).  y_cat [B] int64, y_cont [B][y_cont_dim].
  *   cfg: if guidance > 0 the batch is evaluated as Bt = 2B ([uncond(null token, y_cont=0);

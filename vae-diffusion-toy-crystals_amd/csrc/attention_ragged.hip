@@ -1,0 +1,271 @@
+// Self-attention of SelfAttention2d (sde_score_model.py:136-167) for ANY token count N >= 1: the bottleneck
+// of images whose (H/4)*(W/4) is neither <= 256 nor a multiple of 256 (96^2: N = 576, 72x80: 360, 100^2: 625),
+// which k_attention_mfma (whole head in LDS) and k_attention_flash (256-query blocks, 128-key tiles, no tails)
+// cannot serve.  fp32 products on v_mfma_f32_32x32x2_f32 with the register scheme of attention.hip:
+//   S^T = K Q^T : A = K rows (keys) from LDS, B = Q^T in registers (query on the lane, d split by lane half);
+//   O^T = V^T P^T: the probability accumulators ARE the B operands, key (r&3) + 8(r>>2) + 4 lh of a 32-key
+//                 sub-tile; A = V^T read from LDS in that key order.
+// Its own: the split, the staging and the tails.
+//   split    grid (ceil(N/128), heads, Bt), 4 waves x 32 queries: at N = 576 five 128-row blocks compute 640
+//            rows (a 256-row block: 768), and the 256-thread workgroup with <= 66 KB of LDS fits twice per CU.
+//   staging  64-key tiles in two LDS stages.  The global loads of tile t+1 go to registers BEFORE the MFMAs of
+//            tile t and to the other stage after them, so their latency hides behind ~100 MFMAs; one barrier per
+//            tile (a stage is rewritten only after the barrier that ends the iteration that read it).
+//   key tail only the last tile can be ragged; it is peeled, so the main loop has no masking VALU.  Its source
+//            rows are clamped to N-1 (nothing is read past the tensor), only its ceil(rem/32) live sub-tiles run
+//            (wave-uniform), and the scores of keys >= N are -inf before the row maximum: their p is exactly 0.
+//            Key 0 of every tile is live and sits in lane half 0, so after the xor-32 exchange the tile maximum
+//            is finite and (-inf) - (-inf) never forms.
+//   query tail lanes with q >= N compute on the clamped row N-1; only their stores are guarded.  No wave leaves
+//            before the last barrier: every wave stages, whatever its queries.
+// Online softmax as k_attention_flash: running maximum m, sum l and O^T rescaled by the same factor when a
+// tile raises m; p = exp2((s - m) * scale * log2(e)) on v_exp_f32.  Fixed-order sums, no atomics but the
+// range flag: two runs are bit-equal.
+#include "common.hpp"
+#include "h2.hpp"
+
+namespace tcx {
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int RQ = 128;  // queries per workgroup (4 waves x 32)
+constexpr int RK = 64;   // keys per staged tile (2 sub-tiles of 32)
+
+template <int D>
+struct Ragged {
+    static constexpr int HD = D / 2;            // d per lane half
+    static constexpr int KS = D + 4;            // K row stride ((D+4)/4 odd: conflict-free b128 row reads)
+    static constexpr int DT = (D + 31) / 32;    // 32-row tiles of O^T
+    static constexpr int VS = DT * 32;          // V row stride, zero padded to the tile (lane-per-column reads)
+    static constexpr int D4 = D / 4;
+    static constexpr int ITEMS = RK * D4;       // float4 granules of K (and of V) per tile
+    static constexpr int NU = (ITEMS + 255) / 256;   // per thread
+    static constexpr int STAGE = RK * (KS + VS);     // floats per LDS stage: K rows, then V rows
+    static constexpr size_t LDS = 2 * (size_t)STAGE * sizeof(float);
+};
+
+// One 64-key tile against the wave's 32 queries.  TAIL: the peeled last tile with `rem` (1..64) live keys.
+template <int D, bool TAIL>
+__device__ __forceinline__ void ragged_tile(const float* __restrict__ Ks, const float* __restrict__ Vs,
+                                            const float (&qf)[D / 2], int li, int lh, int rem, float scale2, float& m,
+                                            float& l, f32x16 (&oacc)[(D + 31) / 32]) {
+    using G = Ragged<D>;
+    constexpr int NST = RK / 32;
+    const int nsub = TAIL ? (rem + 31) >> 5 : NST;
+    f32x16 sacc[NST];
+    float mt = -INFINITY;
+#pragma unroll
+    for (int n = 0; n < NST; ++n) {
+        if (TAIL && n >= nsub) continue;
+        sacc[n] = (f32x16){};
+        const float* kr = Ks + (n * 32 + li) * G::KS + G::HD * lh;
+#pragma unroll
+        for (int s4 = 0; s4 < G::HD / 4; ++s4) {
+            const float4 kv = *reinterpret_cast<const float4*>(kr + 4 * s4);
+            sacc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.x, qf[4 * s4 + 0], sacc[n], 0, 0, 0);
+            sacc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.y, qf[4 * s4 + 1], sacc[n], 0, 0, 0);
+            sacc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.z, qf[4 * s4 + 2], sacc[n], 0, 0, 0);
+            sacc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.w, qf[4 * s4 + 3], sacc[n], 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            if (TAIL && n * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh >= rem) sacc[n][r] = -INFINITY;
+            mt = fmaxf(mt, sacc[n][r]);
+        }
+    }
+    mt = fmaxf(mt, __shfl_xor(mt, 32));   // finite: key 0 of the tile is live
+    const float mn = fmaxf(m, mt);
+    const float alpha = __builtin_amdgcn_exp2f((m - mn) * scale2);   // 0 on the first tile (m = -inf)
+    m = mn;
+#pragma unroll
+    for (int t = 0; t < G::DT; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) oacc[t][r] *= alpha;
+    float lt = 0.f;
+#pragma unroll
+    for (int n = 0; n < NST; ++n) {
+        if (TAIL && n >= nsub) continue;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float pv = __builtin_amdgcn_exp2f((sacc[n][r] - mn) * scale2);   // masked key: exp2(-inf) = 0
+            sacc[n][r] = pv;
+            lt += pv;
+        }
+    }
+    lt += __shfl_xor(lt, 32);
+    l = l * alpha + lt;
+#pragma unroll
+    for (int n = 0; n < NST; ++n) {
+        if (TAIL && n >= nsub) continue;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float* vr = Vs + (n * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * G::VS + li;
+#pragma unroll
+            for (int t = 0; t < G::DT; ++t)
+                oacc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(vr[t * 32], sacc[n][r], oacc[t], 0, 0, 0);
+        }
+    }
+}
+
+// 2 waves per SIMD (two workgroups per CU): 256 registers per lane
+template <int D>
+__global__ __launch_bounds__(256, 2) void k_attention_ragged(const float* __restrict__ qkv, void* __restrict__ out,
+                                                             int N, int C, float scale2, int out_h2, unsigned* ovf) {
+    using G = Ragged<D>;
+    extern __shared__ __attribute__((aligned(16))) float sm[];   // stage 0 | stage 1, each K[64][KS] V[64][VS]
+    const int b = blockIdx.z, h = blockIdx.y;
+    const int tid = threadIdx.x;
+    const size_t rs = 3 * (size_t)C;
+    const float* base = qkv + (size_t)b * N * rs + h * D;
+    const int lane = tid & 63, w = tid >> 6;
+    const int li = lane & 31, lh = lane >> 5;
+    const unsigned last = (unsigned)N - 1u;
+    const unsigned q = blockIdx.x * (unsigned)RQ + w * 32 + li;   // unsigned: below N + 127 < 2^32
+    float qf[G::HD];
+    {
+        const float* qs = base + (size_t)min(q, last) * rs + G::HD * lh;
+#pragma unroll
+        for (int s4 = 0; s4 < G::HD / 4; ++s4) {
+            const float4 v = *reinterpret_cast<const float4*>(qs + 4 * s4);
+            qf[4 * s4 + 0] = v.x; qf[4 * s4 + 1] = v.y; qf[4 * s4 + 2] = v.z; qf[4 * s4 + 3] = v.w;
+        }
+    }
+    if (G::VS > D) {   // the V columns past D of both stages: zero, never staged over
+        constexpr int PADW = G::VS > D ? G::VS - D : 1;
+        for (int i = tid; i < 2 * RK * PADW; i += 256) {
+            const int s = i / (RK * PADW), k = i - s * (RK * PADW);
+            const int j = k / PADW, e = k - j * PADW;
+            sm[s * G::STAGE + RK * G::KS + j * G::VS + D + e] = 0.f;
+        }
+    }
+    // staging: thread `tid` owns granules tid, tid + 256, ... of the tile's K and of its V; inlined lambdas and
+    // native vectors (arrays of HIP's float4 struct stayed in scratch: 16 + 32 NU bytes per lane)
+    f32x4 kreg[G::NU], vreg[G::NU];
+    auto fetch = [&](unsigned k0, unsigned lim) __attribute__((always_inline)) {   // lim: the last row a granule may come from
+#pragma unroll
+        for (int u = 0; u < G::NU; ++u) {
+            const int i = tid + 256 * u;
+            if (G::ITEMS % 256 == 0 || i < G::ITEMS) {
+                const int j = i / G::D4, d4 = i - j * G::D4;
+                const unsigned row = min(k0 + j, lim);
+                const float* src = base + (size_t)row * rs + d4 * 4;
+                kreg[u] = *reinterpret_cast<const f32x4*>(src + C);
+                vreg[u] = *reinterpret_cast<const f32x4*>(src + 2 * C);
+            }
+        }
+    };
+    auto stash = [&](float* stage) __attribute__((always_inline)) {
+#pragma unroll
+        for (int u = 0; u < G::NU; ++u) {
+            const int i = tid + 256 * u;
+            if (G::ITEMS % 256 == 0 || i < G::ITEMS) {
+                const int j = i / G::D4, d4 = i - j * G::D4;
+                *reinterpret_cast<f32x4*>(stage + j * G::KS + d4 * 4) = kreg[u];
+                *reinterpret_cast<f32x4*>(stage + RK * G::KS + j * G::VS + d4 * 4) = vreg[u];
+            }
+        }
+    };
+    const unsigned nt = last / RK + 1;   // key tiles; the last has rem = N - (nt-1)*64 in 1..64 live keys
+    fetch(0, last);
+    stash(sm);
+    __syncthreads();
+    f32x16 oacc[G::DT];
+#pragma unroll
+    for (int t = 0; t < G::DT; ++t) oacc[t] = (f32x16){};
+    float m = -INFINITY, l = 0.f;
+    for (unsigned t = 0; t + 1 < nt; ++t) {
+        float* cur = sm + (t & 1) * G::STAGE;
+        float* nxt = sm + ((t & 1) ^ 1) * G::STAGE;
+        fetch((t + 1) * RK, last);   // clamps in the last tile only
+        __builtin_amdgcn_sched_barrier(0);   // keep every load ahead of the tile's MFMAs (the scheduler sank two)
+        ragged_tile<D, false>(cur, cur + RK * G::KS, qf, li, lh, RK, scale2, m, l, oacc);
+        stash(nxt);
+        __syncthreads();   // nxt complete for the next iteration; cur free to be rewritten in it
+    }
+    {
+        const float* cur = sm + ((nt - 1) & 1) * G::STAGE;
+        ragged_tile<D, true>(cur, cur + RK * G::KS, qf, li, lh, (int)(N - (nt - 1) * RK), scale2, m, l, oacc);
+    }
+    if (q >= (unsigned)N) return;   // after the last barrier
+    const float inv = 1.f / l;
+    if (out_h2) {   // h2 record of the query's pixel (h2.hpp): 4 consecutive d per register quad
+        bool bad = false;
+#pragma unroll
+        for (int t = 0; t < G::DT; ++t)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int d = t * 32 + 8 * i + 4 * lh;
+                if (d < D) {
+                    const float4 v = make_float4(oacc[t][4 * i] * inv, oacc[t][4 * i + 1] * inv, oacc[t][4 * i + 2] * inv,
+                                                 oacc[t][4 * i + 3] * inv);
+                    store4_h2(reinterpret_cast<char*>(out), ((size_t)b * N + q) * C * 4, (h * D + d) >> 2, v);
+                    bad = bad || h2_bad(v.x) || h2_bad(v.y) || h2_bad(v.z) || h2_bad(v.w);
+                }
+            }
+        h2_flag(ovf, bad);
+        return;
+    }
+    float* dst = reinterpret_cast<float*>(out) + ((size_t)b * N + q) * C + h * D;
+#pragma unroll
+    for (int t = 0; t < G::DT; ++t)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int d = t * 32 + 8 * i + 4 * lh;
+            if (d < D)
+                *reinterpret_cast<float4*>(dst + d) = make_float4(oacc[t][4 * i] * inv, oacc[t][4 * i + 1] * inv,
+                                                                  oacc[t][4 * i + 2] * inv, oacc[t][4 * i + 3] * inv);
+        }
+}
+
+template <int D>
+int launch_attn_ragged(const float* qkv, void* out, int out_h2, int Bt, int N, int C, int heads, unsigned* ovf,
+                       hipStream_t st) {
+    // log2(e) / sqrt(D): the logits in exp2 units
+    const float scale2 = (float)(1.4426950408889634 / std::sqrt((double)D));
+    static bool attr_set = false;   // 66 KB at D = 64: above 64 KB dynamic LDS needs the explicit opt-in
+    if (!attr_set) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attention_ragged<D>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)Ragged<D>::LDS) != hipSuccess) {
+            set_error("tcx_attention_ragged: cannot enable %zu B of dynamic LDS", Ragged<D>::LDS);
+            return TCX_EHIP;
+        }
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((k_attention_ragged<D>), dim3((N - 1) / RQ + 1, heads, Bt), dim3(256), Ragged<D>::LDS, st, qkv, out,
+                       N, C, scale2, out_h2, ovf);
+    return check_launch("tcx_attention_ragged");
+}
+
+}  // namespace
+}  // namespace tcx
+
+using namespace tcx;
+
+extern "C" int tcx_attention_ragged(const float* qkv, void* out, int out_h2, int Bt, int N, int C, int heads,
+                                    unsigned* ovf, void* stream) {
+    TCX_REQUIRE(qkv && out, "tcx_attention_ragged: null pointer");
+    TCX_REQUIRE(heads > 0 && C > 0 && C % heads == 0, "tcx_attention_ragged: bad args (need heads > 0, C %% heads == 0)");
+    TCX_REQUIRE(N > 0, "tcx_attention_ragged: N must be >= 1");
+    TCX_REQUIRE(out_h2 == 0 || out_h2 == 1, "tcx_attention_ragged: out_h2 must be 0 (fp32) or 1 (h2 records)");
+    TCX_REQUIRE(!out_h2 || C % 8 == 0, "tcx_attention_ragged: h2 output needs C %% 8 == 0");
+    TCX_REQUIRE(aligned16(qkv) && aligned16(out), "tcx_attention_ragged: pointers must be 16-B aligned");
+    TCX_REQUIRE(Bt >= 0 && Bt <= 65535, "tcx_attention_ragged: Bt must be in [0, 65535] (one grid row per image)");
+    TCX_REQUIRE(heads <= 65535, "tcx_attention_ragged: heads must be in [1, 65535] (one grid row per head)");
+    const int D = C / heads;
+    if (!(D == 8 || D == 16 || D == 24 || D == 32 || D == 48 || D == 64)) {
+        set_error("tcx_attention_ragged: head dim %d unsupported (8, 16, 24, 32, 48 or 64)", D);
+        return TCX_EUNSUP;
+    }
+    if (Bt == 0) return TCX_OK;
+    hipStream_t st = (hipStream_t)stream;
+    switch (D) {
+        case 8: return launch_attn_ragged<8>(qkv, out, out_h2, Bt, N, C, heads, ovf, st);
+        case 16: return launch_attn_ragged<16>(qkv, out, out_h2, Bt, N, C, heads, ovf, st);
+        case 24: return launch_attn_ragged<24>(qkv, out, out_h2, Bt, N, C, heads, ovf, st);
+        case 32: return launch_attn_ragged<32>(qkv, out, out_h2, Bt, N, C, heads, ovf, st);
+        case 48: return launch_attn_ragged<48>(qkv, out, out_h2, Bt, N, C, heads, ovf, st);
+        default: return launch_attn_ragged<64>(qkv, out, out_h2, Bt, N, C, heads, ovf, st);
+    }
+}

@@ -264,7 +264,11 @@ int unet_body(const tcx_unet* net, const Plan& P, const float* x, int B, const f
             qa.pad = 0;
             TCX_TRY(conv_gn(q, st, qa));
             TCX_REQUIRE(split_attn || !h2.bf, "tcx_unet: bf16 precision needs the split attention (N %% 256 == 0)");
+            // a token count neither <= 256 nor a multiple of 256 (96x96: 576): the any-N fp32-MFMA kernel
+            const bool ragged = P.P2 > 256 && P.P2 % 256 != 0;
             if (split_attn) TCX_TRY(attention_split(P.qkv, P.b16, Bt, P.P2, C2, net->heads, fmt, st));
+            else if (ragged)
+                TCX_TRY(tcx_attention_ragged(P.qkv, P.b16, h2.on ? 1 : 0, Bt, P.P2, C2, net->heads, h2.ovf, st));
             else if (h2.on) TCX_TRY(tcx_attention_h2(P.qkv, P.b16, Bt, P.P2, C2, net->heads, h2.ovf, st));
             else TCX_TRY(tcx_attention(P.qkv, P.b16, Bt, P.P2, C2, net->heads, st));
             ConvGn pa = layer(P.b16, C2, H2, W2, P.a16);  // 1x1, + x_in
@@ -338,8 +342,7 @@ int validate(const tcx_unet* net, int B, int H, int W) {
     TCX_REQUIRE(net->base_ch % 4 == 0 && net->base_ch >= 4, "tcx_unet: base_ch must be a multiple of 4");
     TCX_REQUIRE(net->emb_dim <= 256 && net->emb_dim % 2 == 0, "tcx_unet: emb_dim must be even and <= 256");
     TCX_REQUIRE(net->time_ch + net->cond_ch <= 64 && net->y_cont_dim >= 3 && net->y_cont_dim <= 16, "tcx_unet: bad cond dims");
-    TCX_REQUIRE((H / 4) * (W / 4) <= 256 || ((H / 4) * (W / 4)) % 256 == 0,
-                "tcx_unet: bottleneck attention needs N <= 256 or N %% 256 == 0 tokens");
+    // (any token count (H/4)*(W/4): tcx_attention_ragged serves what the other attention kernels do not)
     TCX_REQUIRE(net->precision >= 0 && net->precision <= 2,
                 "tcx_unet: precision must be 0 (fp32), 1 (f16x3) or 2 (bf16)");
     TCX_REQUIRE(net->precision == 0 || (net->base_ch % 32 == 0 && ((H / 4) * (W / 4)) % 32 == 0),

@@ -70,7 +70,8 @@ def main() -> int:
             f"_steps{args.steps}_cfg{args.cfg:.2f}_tend{args.t_end:g}_samplerdpmpp{args.order}_ema{args.use_ema}.png")
     save_sde_samples(model=model, sde=sde, out_path=args.out_path, device=device, n=args.n,
                      theta_max=args.theta_max, steps=args.steps, cfg=args.cfg, t_end=args.t_end, sampler="dpmpp",
-                     dpmpp=dict(order=args.order, lower_order_final=bool(args.lower_order_final)))
+                     dpmpp=dict(order=args.order, lower_order_final=bool(args.lower_order_final)),
+                     img_size=int(cfg.get("img_size", 64)))
     print(f"Saved samples -> {args.out_path}")
     return 0
 

@@ -74,7 +74,8 @@ def main() -> int:
             f"samples_ckpt-{os.path.splitext(os.path.basename(ckpt_path))[0]}"
             f"_steps{args.steps}_cfg{args.cfg:.2f}_tend{args.t_end:g}_sampler{args.sampler}_ema{args.use_ema}.png")
     save_sde_samples(model=model, sde=sde, out_path=args.out_path, device=device, n=args.n,
-                     theta_max=args.theta_max, steps=args.steps, cfg=args.cfg, t_end=args.t_end, sampler=args.sampler)
+                     theta_max=args.theta_max, steps=args.steps, cfg=args.cfg, t_end=args.t_end, sampler=args.sampler,
+                     img_size=int(cfg.get("img_size", 64)))  # a checkpoint whose config records its image size
     print(f"Saved samples -> {args.out_path}")
     return 0
 

@@ -487,10 +487,10 @@ def dpmpp_table(sde: VPSDE, n_steps: int, t_end: float, order: int = 2,
 @torch.no_grad()
 def save_sde_samples(model: CondUNetTiny, sde: VPSDE, out_path: str, device: torch.device, n: int = 36,
                      theta_max: float = math.pi / 3.0, steps: int = 200, cfg: float = 0.0, t_end: float = 1e-3,
-                     sampler: str = "ode", *, dpmpp: Optional[dict] = None) -> None:
+                     sampler: str = "ode", *, dpmpp: Optional[dict] = None, img_size: int = 64) -> None:
     """Save a 6x6 grid: cycle lattice types, sweep theta in [0, pi/3] (sde_score_model.py:301-355).
     sampler="dpmpp" (not in the reference) is sample_dpm_solver_pp; `dpmpp` holds its own keywords
-    (order, lower_order_final)."""
+    (order, lower_order_final).  `img_size` (the reference samples at 64): any multiple of 4, at least 8."""
     import matplotlib
     matplotlib.use("Agg")
     import matplotlib.pyplot as plt
@@ -500,7 +500,7 @@ def save_sde_samples(model: CondUNetTiny, sde: VPSDE, out_path: str, device: tor
     thetas = torch.linspace(0.0, theta_max, steps=n, device=device)
     y_cont = torch.zeros((n, model.y_cont_dim), device=device)
     y_cont[:, 1] = thetas
-    kw = dict(model=model, sde=sde, y_cat=y_cat, y_cont=y_cont, img_shape=(n, 1, 64, 64), n_steps=steps,
+    kw = dict(model=model, sde=sde, y_cat=y_cat, y_cont=y_cont, img_shape=(n, 1, img_size, img_size), n_steps=steps,
               guidance_scale=cfg, t_end=t_end)
     if sampler == "ode":
         x = sample_probability_flow_ode(**kw)
