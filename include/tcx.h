@@ -662,6 +662,21 @@ size_t tcx_attention_bwd_workspace(int Bt, int N, int C, int heads);
 int tcx_attention_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv,
                       int Bt, int N, int C, int heads, void* ws, size_t ws_bytes, void* stream);
 
+/* The same pair for ANY token count N >= 1 (k_attention_ragged<D, true>, k_attn_rbwd_dq / _dkv): head dim
+ * 8,16,24,32,48,64 (another: TCX_EUNSUP), Bt in [0, 65535], heads in [1, 65535], every pointer (ws included)
+ * 16-B aligned.  tcx_attention_ragged_fwd_lse: `out` (fp32) bit-identical to tcx_attention_ragged(out_h2 = 0),
+ * lse [Bt][heads][N] = m * scale + ln l (natural log, m the raw row maximum, scale = 1/sqrt(C/heads)).
+ * tcx_attention_ragged_bwd: dqkv [Bt,N,3C] (every element written) from qkv, out, dout [Bt,N,C] and that lse,
+ * without any N x N tensor; fixed-order sums, two runs bit-equal.  ws: tcx_attention_ragged_bwd_workspace
+ * bytes (delta, Bt*heads*N floats); short or NULL is TCX_EWS with the required size in the message.  Bt == 0
+ * returns TCX_OK and writes nothing.  Every refusal comes before any launch.  The workspace query returns 0
+ * for an unsupported head dim or bad arguments: callers use it as the predicate. */
+int tcx_attention_ragged_fwd_lse(const float* qkv, float* out, float* lse, int Bt, int N, int C, int heads,
+                                 void* stream);
+size_t tcx_attention_ragged_bwd_workspace(int Bt, int N, int C, int heads);
+int tcx_attention_ragged_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv,
+                             int Bt, int N, int C, int heads, void* ws, size_t ws_bytes, void* stream);
+
 /* Elementwise activation (1 ReLU, 2 Sigmoid, 3 SiLU) and its backward from the pre-activation. */
 int tcx_act_fwd(const float* z, float* y, size_t n, int act, void* stream);
 int tcx_act_bwd(const float* z, const float* dy, float* dz, size_t n, int act, void* stream);

@@ -110,9 +110,11 @@ __device__ __forceinline__ void ragged_tile(const float* __restrict__ Ks, const 
 }
 
 // 2 waves per SIMD (two workgroups per CU): 256 registers per lane
-template <int D>
+// LSE: the training forward (tcx_attention_ragged_fwd_lse), which also stores the row log-sum-exp
+template <int D, bool LSE = false>
 __global__ __launch_bounds__(256, 2) void k_attention_ragged(const float* __restrict__ qkv, void* __restrict__ out,
-                                                             int N, int C, float scale2, int out_h2, unsigned* ovf) {
+                                                             int N, int C, float scale2, int out_h2, unsigned* ovf,
+                                                             float* __restrict__ lse, float scale) {
     using G = Ragged<D>;
     extern __shared__ __attribute__((aligned(16))) float sm[];   // stage 0 | stage 1, each K[64][KS] V[64][VS]
     const int b = blockIdx.z, h = blockIdx.y;
@@ -190,6 +192,7 @@ __global__ __launch_bounds__(256, 2) void k_attention_ragged(const float* __rest
     }
     if (q >= (unsigned)N) return;   // after the last barrier
     const float inv = 1.f / l;
+    if (LSE && lh == 0) lse[((size_t)b * gridDim.y + h) * N + q] = m * scale + logf(l);
     if (out_h2) {   // h2 record of the query's pixel (h2.hpp): 4 consecutive d per register quad
         bool bad = false;
 #pragma unroll
@@ -219,23 +222,24 @@ __global__ __launch_bounds__(256, 2) void k_attention_ragged(const float* __rest
         }
 }
 
-template <int D>
+template <int D, bool LSE = false>
 int launch_attn_ragged(const float* qkv, void* out, int out_h2, int Bt, int N, int C, int heads, unsigned* ovf,
-                       hipStream_t st) {
+                       hipStream_t st, float* lse = nullptr) {
     // log2(e) / sqrt(D): the logits in exp2 units
     const float scale2 = (float)(1.4426950408889634 / std::sqrt((double)D));
+    const float scale = (float)(1.0 / std::sqrt((double)D));
     static bool attr_set = false;   // 66 KB at D = 64: above 64 KB dynamic LDS needs the explicit opt-in
     if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attention_ragged<D>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attention_ragged<D, LSE>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)Ragged<D>::LDS) != hipSuccess) {
             set_error("tcx_attention_ragged: cannot enable %zu B of dynamic LDS", Ragged<D>::LDS);
             return TCX_EHIP;
         }
         attr_set = true;
     }
-    hipLaunchKernelGGL((k_attention_ragged<D>), dim3((N - 1) / RQ + 1, heads, Bt), dim3(256), Ragged<D>::LDS, st, qkv, out,
-                       N, C, scale2, out_h2, ovf);
-    return check_launch("tcx_attention_ragged");
+    hipLaunchKernelGGL((k_attention_ragged<D, LSE>), dim3((N - 1) / RQ + 1, heads, Bt), dim3(256), Ragged<D>::LDS, st, qkv,
+                       out, N, C, scale2, out_h2, ovf, lse, scale);
+    return check_launch(LSE ? "tcx_attention_ragged_fwd_lse" : "tcx_attention_ragged");
 }
 
 }  // namespace
@@ -267,5 +271,34 @@ extern "C" int tcx_attention_ragged(const float* qkv, void* out, int out_h2, int
         case 32: return launch_attn_ragged<32>(qkv, out, out_h2, Bt, N, C, heads, ovf, st);
         case 48: return launch_attn_ragged<48>(qkv, out, out_h2, Bt, N, C, heads, ovf, st);
         default: return launch_attn_ragged<64>(qkv, out, out_h2, Bt, N, C, heads, ovf, st);
+    }
+}
+
+// The training forward for any N: k_attention_ragged<D, true>, fp32 out bit-equal to tcx_attention_ragged(out_h2 = 0)
+// plus lse[b][h][q] = m * scale + ln l for tcx_attention_ragged_bwd.
+extern "C" int tcx_attention_ragged_fwd_lse(const float* qkv, float* out, float* lse, int Bt, int N, int C, int heads,
+                                            void* stream) {
+    TCX_REQUIRE(qkv && out && lse, "tcx_attention_ragged_fwd_lse: null pointer");
+    TCX_REQUIRE(heads > 0 && C > 0 && C % heads == 0,
+                "tcx_attention_ragged_fwd_lse: bad args (need heads > 0, C %% heads == 0)");
+    TCX_REQUIRE(N > 0, "tcx_attention_ragged_fwd_lse: N must be >= 1");
+    TCX_REQUIRE(aligned16(qkv) && aligned16(out) && aligned16(lse),
+                "tcx_attention_ragged_fwd_lse: pointers must be 16-B aligned");
+    TCX_REQUIRE(Bt >= 0 && Bt <= 65535, "tcx_attention_ragged_fwd_lse: Bt must be in [0, 65535] (one grid row per image)");
+    TCX_REQUIRE(heads <= 65535, "tcx_attention_ragged_fwd_lse: heads must be in [1, 65535] (one grid row per head)");
+    const int D = C / heads;
+    if (!(D == 8 || D == 16 || D == 24 || D == 32 || D == 48 || D == 64)) {
+        set_error("tcx_attention_ragged_fwd_lse: head dim %d unsupported (8, 16, 24, 32, 48 or 64)", D);
+        return TCX_EUNSUP;
+    }
+    if (Bt == 0) return TCX_OK;
+    hipStream_t st = (hipStream_t)stream;
+    switch (D) {
+        case 8: return launch_attn_ragged<8, true>(qkv, out, 0, Bt, N, C, heads, nullptr, st, lse);
+        case 16: return launch_attn_ragged<16, true>(qkv, out, 0, Bt, N, C, heads, nullptr, st, lse);
+        case 24: return launch_attn_ragged<24, true>(qkv, out, 0, Bt, N, C, heads, nullptr, st, lse);
+        case 32: return launch_attn_ragged<32, true>(qkv, out, 0, Bt, N, C, heads, nullptr, st, lse);
+        case 48: return launch_attn_ragged<48, true>(qkv, out, 0, Bt, N, C, heads, nullptr, st, lse);
+        default: return launch_attn_ragged<64, true>(qkv, out, 0, Bt, N, C, heads, nullptr, st, lse);
     }
 }

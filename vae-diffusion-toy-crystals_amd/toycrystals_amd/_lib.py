@@ -189,6 +189,10 @@ _SIGS = {
     "tcx_attention_fwd_lse": (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
     "tcx_attention_bwd_workspace": (c_size, [c_int, c_int, c_int, c_int]),
     "tcx_attention_bwd": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_size, c_fp]),
+    "tcx_attention_ragged_fwd_lse": (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
+    "tcx_attention_ragged_bwd_workspace": (c_size, [c_int, c_int, c_int, c_int]),
+    "tcx_attention_ragged_bwd": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_size,
+                                         c_fp]),
     "tcx_act_fwd": (c_int, [c_fp, c_fp, c_size, c_int, c_fp]),
     "tcx_act_bwd": (c_int, [c_fp, c_fp, c_fp, c_size, c_int, c_fp]),
     "tcx_mse_loss": (c_int, [c_fp, c_fp, c_size, c_fp, c_fp, c_size, c_fp]),

@@ -514,7 +514,9 @@ class Upsample2xFn(torch.autograd.Function):
 # ---------------------------------------------------------------- attention
 # Fused training attention (csrc/attention_bwd.hip): the forward keeps only the row log-sum-exp and the
 # backward recomputes P tile by tile, so no [B, heads, N, N] tensor exists (the GEMM chain below passes
-# four of them through HBM per step).  TCX_ATTN_FUSED=0 keeps the chain for every shape (A/B).
+# four of them through HBM per step).  Token counts outside that pair's set (96x96: N = 576) run its any-N
+# siblings (csrc/attention_ragged.hip, csrc/attention_ragged_bwd.hip).  TCX_ATTN_FUSED=0 keeps the chain for
+# every shape (A/B).
 _ATTN_FUSED = os.environ.get("TCX_ATTN_FUSED", "1") != "0"
 
 
@@ -522,6 +524,12 @@ def _attn_fused_ok(N: int, C: int, heads: int) -> bool:
     """the shapes tcx_attention_fwd_lse / tcx_attention_bwd serve (the library's own predicate: a workspace
     size of 0 means outside the set); any other runs the GEMM chain"""
     return _ATTN_FUSED and lib().tcx_attention_bwd_workspace(1, N, C, heads) > 0
+
+
+def _attn_ragged_ok(N: int, C: int, heads: int) -> bool:
+    """any other N at a head dim tcx_attention_ragged_fwd_lse / tcx_attention_ragged_bwd serve (8 .. 64); the
+    rest (the d = 4 heads of the base_ch-16 nets) runs the GEMM chain"""
+    return _ATTN_FUSED and lib().tcx_attention_ragged_bwd_workspace(1, N, C, heads) > 0
 
 
 class AttentionFn(torch.autograd.Function):
@@ -536,10 +544,15 @@ class AttentionFn(torch.autograd.Function):
         d = C // heads
         ctx.heads = heads
         ctx.fused = _attn_fused_ok(N, C, heads)
-        if ctx.fused:
+        ctx.ragged = not ctx.fused and _attn_ragged_ok(N, C, heads)
+        if ctx.fused or ctx.ragged:
             out, lse = _empty((B, N, C), qkv), _empty((B, heads, N), qkv)
-            check(L.tcx_attention_fwd_lse(ptr(qkv), ptr(out), ptr(lse), B, N, C, heads, _st(qkv)),
-                  "tcx_attention_fwd_lse")
+            if ctx.fused:
+                check(L.tcx_attention_fwd_lse(ptr(qkv), ptr(out), ptr(lse), B, N, C, heads, _st(qkv)),
+                      "tcx_attention_fwd_lse")
+            else:
+                check(L.tcx_attention_ragged_fwd_lse(ptr(qkv), ptr(out), ptr(lse), B, N, C, heads, _st(qkv)),
+                      "tcx_attention_ragged_fwd_lse")
             ctx.save_for_backward(qkv, out, lse)
             return out
         scale = 1.0 / math.sqrt(d)
@@ -567,6 +580,15 @@ class AttentionFn(torch.autograd.Function):
             dqkv = torch.empty_like(qkv)
             check(L.tcx_attention_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), B, N, C3 // 3, heads,
                                       ptr(ws), ws.numel(), _st(qkv)), "tcx_attention_bwd")
+            return dqkv, None
+        if ctx.ragged:
+            qkv, out, lse = ctx.saved_tensors
+            B, N, C3 = qkv.shape
+            nb = int(L.tcx_attention_ragged_bwd_workspace(B, N, C3 // 3, heads))
+            ws = _ws(qkv.device, nb)
+            dqkv = torch.empty_like(qkv)
+            check(L.tcx_attention_ragged_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), B, N, C3 // 3, heads,
+                                             ptr(ws), ws.numel(), _st(qkv)), "tcx_attention_ragged_bwd")
             return dqkv, None
         qkv, P = ctx.saved_tensors
         B, N, C3 = qkv.shape
