@@ -281,6 +281,15 @@ int tcx_attention(const float* qkv, float* out, int Bt, int N, int C, int heads,
  * (H/4)*(W/4) is above 256 and no multiple of 256 (96x96: 576 tokens). */
 int tcx_attention_ragged(const float* qkv, void* out, int out_h2, int Bt, int N, int C, int heads,
                          unsigned* ovf, void* stream);
+/* The three tcx_attention_split* forms for every token count: any N >= 1 (k_attention_split_ragged,
+ * csrc/attention_split_ragged.hip: 128-query workgroups, 64-key tiles, a peeled and masked last tile).
+ * qkv and out in one storage format, fmt: 0 h2 records (f16x3 products), 1 bf16 records (one bf16 product
+ * of the hi halves, the output with both halves), 2 two-byte bf16.  Head dim 16, 32, 48 or 64 (else
+ * TCX_EUNSUP).  Same Bt / heads bounds; Bt == 0 returns TCX_OK and writes nothing.  No range flag: the output
+ * is a convex combination of V rows.  The score U-Net evaluator runs its bottleneck here at precision 2 when
+ * (H/4)*(W/4) is no multiple of 256 (96x96: 576 tokens, 32x32: 64). */
+int tcx_attention_split_ragged(const void* qkv, void* out, int fmt, int Bt, int N, int C, int heads,
+                               void* stream);
 
 /* ------------------------------------------------------------------ score U-Net */
 
@@ -315,9 +324,12 @@ typedef struct tcx_unet {
      * activations (needs base_ch % 32 == 0, (H/4)*(W/4) % 32 == 0 and every conv's wh/wscale); h2_ovf:
      * device word raised when an activation leaves the f16 range (the host re-runs the evaluation in
      * fp32); 2: bf16 single-product convs and attention over bf16 records (wh/whf/wscale then hold the
-     * tcx_pack_conv_weight_bf16 packs; (H/4)*(W/4) % 256 == 0).  The bottleneck attention of N =
-     * (H/4)*(W/4) tokens: N <= 256 or N % 256 == 0 on the kernels of tcx_attention / _h2 / _split, any
-     * other N (precision 0 and 1) on fp32 MFMA by tcx_attention_ragged. */
+     * tcx_pack_conv_weight_bf16 packs; the same size conditions as 1).  The bottleneck attention of N =
+     * (H/4)*(W/4) tokens: N <= 256 or N % 256 == 0 on the kernels of tcx_attention / _h2 / _split (precision
+     * 2: N % 256 == 0 on tcx_attention_split_bf16 / _b2, every other N on tcx_attention_split_ragged).  N above
+     * 256 and no multiple of 256: precision 0 on fp32 MFMA by tcx_attention_ragged; precision 1 on whichever
+     * of tcx_attention_split_ragged (h2 qkv) and tcx_attention_ragged measured faster end to end
+     * (TCX_ATTN_SPLIT_RAGGED = 1 / 0 selects; OPTLOG.md). */
     int precision;
     unsigned* h2_ovf;
 } tcx_unet;

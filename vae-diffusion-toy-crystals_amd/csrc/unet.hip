@@ -155,6 +155,9 @@ int unet_body(const tcx_unet* net, const Plan& P, const float* x, int B, const f
     static const bool attn_prep_on = env_on("TCX_ATTN_PREP");
     // TCX_ATTN_SPLIT=0 keeps the split evaluator's attention on fp32 MFMA (A/B measurements)
     static const bool attn_split_on = env_on("TCX_ATTN_SPLIT");
+    // TCX_ATTN_SPLIT_RAGGED=0: f16x3 at a token count above 256 with tails (96x96) keeps fp32 qkv and
+    // tcx_attention_ragged instead of h2 qkv and k_attention_split_ragged (A/B; OPTLOG.md round 15)
+    static const bool split_ragged_f16 = env_on("TCX_ATTN_SPLIT_RAGGED");
     // TCX_ATTN_BLOCK=0: the bottleneck attention as three launches (qkv conv, k_attention_split, proj conv)
     // instead of k_attn_block + proj (bit-identical; A/B measurements and parity tests)
     static const bool attn_block_on = env_on("TCX_ATTN_BLOCK");
@@ -247,11 +250,15 @@ int unet_body(const tcx_unet* net, const Plan& P, const float* x, int B, const f
         }
         const tcx_conv& q = net->qkv;
         const tcx_conv& pr = net->proj;
-        // split path with N % 256 == 0 and a supported head dim: the qkv conv writes h2 and the
-        // attention runs on f16x3 MFMA (attention_split.hip); else fp32 qkv + fp32-MFMA attention
+        // split path with a supported head dim: the qkv conv writes the evaluation's format and the attention
+        // runs on f16x3 / bf16 MFMA: N % 256 == 0 on k_attention_split; a token count with tails (96x96: 576,
+        // 32x32: 64) on k_attention_split_ragged, at bf16 always (its only attention) and at f16x3 above 256
+        // tokens where split_ragged_f16 says so.  Else fp32 qkv + fp32-MFMA attention
         const int D = C2 / net->heads;
-        const bool split_attn = h2.on && attn_split_on && P.P2 % 256 == 0 && C2 % net->heads == 0 &&
-                                (D == 16 || D == 32 || D == 48 || D == 64);
+        const bool tails = P.P2 % 256 != 0;
+        const bool split_attn = h2.on && attn_split_on && C2 % net->heads == 0 &&
+                                (D == 16 || D == 32 || D == 48 || D == 64) &&
+                                (!tails || h2.bf || (P.P2 > 256 && split_ragged_f16));
         // f16x3 at N = 256, C2 = 192, 4 heads: the qkv conv runs inside the attention workgroup
         // (attn_block.hip; its output goes to the free qkv buffer, since the heads of an image read b16
         // while others already write), then the proj launch as below
@@ -263,10 +270,13 @@ int unet_body(const tcx_unet* net, const Plan& P, const float* x, int B, const f
             ConvGn qa = layer(P.b16, C2, H2, W2, P.qkv, split_attn ? 1 : 0);  // 1x1
             qa.pad = 0;
             TCX_TRY(conv_gn(q, st, qa));
-            TCX_REQUIRE(split_attn || !h2.bf, "tcx_unet: bf16 precision needs the split attention (N %% 256 == 0)");
+            TCX_REQUIRE(split_attn || !h2.bf,
+                        "tcx_unet: bf16 precision needs the split attention (head dim 16, 32, 48 or 64; TCX_ATTN_SPLIT on)");
             // a token count neither <= 256 nor a multiple of 256 (96x96: 576): the any-N fp32-MFMA kernel
-            const bool ragged = P.P2 > 256 && P.P2 % 256 != 0;
-            if (split_attn) TCX_TRY(attention_split(P.qkv, P.b16, Bt, P.P2, C2, net->heads, fmt, st));
+            const bool ragged = P.P2 > 256 && tails;
+            if (split_attn && tails)
+                TCX_TRY(tcx_attention_split_ragged(P.qkv, P.b16, fmt, Bt, P.P2, C2, net->heads, st));
+            else if (split_attn) TCX_TRY(attention_split(P.qkv, P.b16, Bt, P.P2, C2, net->heads, fmt, st));
             else if (ragged)
                 TCX_TRY(tcx_attention_ragged(P.qkv, P.b16, h2.on ? 1 : 0, Bt, P.P2, C2, net->heads, h2.ovf, st));
             else if (h2.on) TCX_TRY(tcx_attention_h2(P.qkv, P.b16, Bt, P.P2, C2, net->heads, h2.ovf, st));
@@ -347,8 +357,7 @@ int validate(const tcx_unet* net, int B, int H, int W) {
                 "tcx_unet: precision must be 0 (fp32), 1 (f16x3) or 2 (bf16)");
     TCX_REQUIRE(net->precision == 0 || (net->base_ch % 32 == 0 && ((H / 4) * (W / 4)) % 32 == 0),
                 "tcx_unet: the split paths need base_ch %% 32 == 0 and (H/4)*(W/4) %% 32 == 0");
-    TCX_REQUIRE(net->precision != 2 || ((H / 4) * (W / 4)) % 256 == 0,
-                "tcx_unet: bf16 precision needs (H/4)*(W/4) %% 256 == 0 (the split attention)");
+    // (bf16 at any such token count: k_attention_split_ragged serves what k_attention_split does not)
     return TCX_OK;
 }
 

@@ -104,6 +104,7 @@ _SIGS = {
     "tcx_upsample2x_bf16": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp]),
     "tcx_attention_split_bf16": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
     "tcx_attention_split_b2": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
+    "tcx_attention_split_ragged": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_fp]),
     "tcx_gn_apply_tab_b2": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_fp, c_fp, c_int, c_int, c_fp]),
     "tcx_upsample2x_b2": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp]),
     "tcx_conv_weight_h2_frag_bytes": (c_size, [c_int, c_int]),
@@ -247,8 +248,8 @@ def conv_precision() -> str:
     return _conv_precision
 
 
-# the precision the score U-Net evaluator actually ran its last call in ("bf16" falls back to f16x3
-# where the split attention does not apply, any split run to fp32 after a range overflow); bench.py
+# the precision the score U-Net evaluator actually ran its last call in ("bf16" and "f16x3" fall back to
+# fp32 where the split path does not apply, any split run to fp32 after a range overflow); bench.py
 # reports this, not the requested one
 _used_precision = None
 

@@ -240,14 +240,16 @@ class _UNetPack:
     def run(self, H: int, W: int, launch) -> None:
         """Run `launch()` (which must (re)initialise its outputs) with the configured conv
         precision; if an f16x3 run raised the range flag, re-run it in fp32 (one host sync).
-        "bf16" (config 5's precision) runs where the split attention applies, else f16x3."""
+        "bf16" (config 5's precision) runs wherever the split path does: base_ch % 32 == 0 and a bottleneck
+        token count (H/4)*(W/4) % 32 == 0 (96x96 and 32x32 included: tcx_attention_split_ragged serves the
+        counts that are no multiple of 256); elsewhere it warns once and runs fp32."""
         prec = _lib.conv_precision()
         split = prec in ("f16x3", "bf16") and self.split_ok and ((H // 4) * (W // 4)) % 32 == 0
-        bf = split and prec == "bf16" and ((H // 4) * (W // 4)) % 256 == 0
+        bf = split and prec == "bf16"
         if prec == "bf16" and not bf and not self._warned_bf16:
             self._warned_bf16 = True
-            warnings.warn(f"libtcx: bf16 precision needs (H/4)*(W/4) % 256 == 0 (the split attention); "
-                          f"{H}x{W} runs in {'f16x3' if split else 'fp32'}")
+            warnings.warn(f"libtcx: bf16 precision needs base_ch % 32 == 0 and (H/4)*(W/4) % 32 == 0 (the split "
+                          f"path); {H}x{W} runs in fp32")
         _lib.note_used_precision("bf16" if bf else ("f16x3" if split else "fp32"))
         if bf:
             saved = {}
