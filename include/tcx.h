@@ -281,6 +281,13 @@ int tcx_attention(const float* qkv, float* out, int Bt, int N, int C, int heads,
  * (H/4)*(W/4) is above 256 and no multiple of 256 (96x96: 576 tokens). */
 int tcx_attention_ragged(const float* qkv, void* out, int out_h2, int Bt, int N, int C, int heads,
                          unsigned* ovf, void* stream);
+/* tcx_attention_ragged's interface at the wide head dims 80, 96 and 128 (another: TCX_EUNSUP), any N >= 1
+ * (k_attention_wide, csrc/attention_wide.hip: 128-query workgroups, 32-key tiles in two LDS stages, a peeled
+ * and masked last tile; fp32 MFMA, online softmax, two runs bit-equal).  out_h2 = 0: out is fp32, ovf ignored;
+ * 1: out is h2 records, ovf as in tcx_attention_h2.  Same Bt / heads bounds; Bt == 0 returns TCX_OK and writes
+ * nothing.  The score U-Net evaluator runs its bottleneck here whenever base_ch / 2 is 80, 96 or 128. */
+int tcx_attention_wide(const float* qkv, void* out, int out_h2, int Bt, int N, int C, int heads,
+                       unsigned* ovf, void* stream);
 /* The three tcx_attention_split* forms for every token count: any N >= 1 (k_attention_split_ragged,
  * csrc/attention_split_ragged.hip: 128-query workgroups, 64-key tiles, a peeled and masked last tile).
  * qkv and out in one storage format, fmt: 0 h2 records (f16x3 products), 1 bf16 records (one bf16 product
@@ -688,6 +695,15 @@ int tcx_attention_ragged_fwd_lse(const float* qkv, float* out, float* lse, int B
 size_t tcx_attention_ragged_bwd_workspace(int Bt, int N, int C, int heads);
 int tcx_attention_ragged_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv,
                              int Bt, int N, int C, int heads, void* ws, size_t ws_bytes, void* stream);
+
+/* The same pair, same contract, at head dim 80, 96 or 128 (another: TCX_EUNSUP, workspace query 0) for any
+ * N >= 1 (k_attention_wide<D, true>, k_attn_wbwd_dq / _dkv: csrc/attention_wide.hip, attention_wide_bwd.hip).
+ * `out` of tcx_attention_wide_fwd_lse is bit-identical to tcx_attention_wide(out_h2 = 0). */
+int tcx_attention_wide_fwd_lse(const float* qkv, float* out, float* lse, int Bt, int N, int C, int heads,
+                               void* stream);
+size_t tcx_attention_wide_bwd_workspace(int Bt, int N, int C, int heads);
+int tcx_attention_wide_bwd(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv,
+                           int Bt, int N, int C, int heads, void* ws, size_t ws_bytes, void* stream);
 
 /* Elementwise activation (1 ReLU, 2 Sigmoid, 3 SiLU) and its backward from the pre-activation. */
 int tcx_act_fwd(const float* z, float* y, size_t n, int act, void* stream);

@@ -271,12 +271,17 @@ int unet_body(const tcx_unet* net, const Plan& P, const float* x, int B, const f
             qa.pad = 0;
             TCX_TRY(conv_gn(q, st, qa));
             TCX_REQUIRE(split_attn || !h2.bf,
-                        "tcx_unet: bf16 precision needs the split attention (head dim 16, 32, 48 or 64; TCX_ATTN_SPLIT on)");
+                        "tcx_unet: bf16 precision needs the split attention (head dim 16, 32, 48 or 64; TCX_ATTN_SPLIT on); "
+                        "the wide head dims 80, 96 and 128 evaluate at fp32 and f16x3 only");
             // a token count neither <= 256 nor a multiple of 256 (96x96: 576): the any-N fp32-MFMA kernel
             const bool ragged = P.P2 > 256 && tails;
+            // head dim 80, 96 or 128 (base_ch 160 / 192 / 256 at four heads): the wide kernel at every token count
+            const bool wide = C2 % net->heads == 0 && (D == 80 || D == 96 || D == 128);
             if (split_attn && tails)
                 TCX_TRY(tcx_attention_split_ragged(P.qkv, P.b16, fmt, Bt, P.P2, C2, net->heads, st));
             else if (split_attn) TCX_TRY(attention_split(P.qkv, P.b16, Bt, P.P2, C2, net->heads, fmt, st));
+            else if (wide)
+                TCX_TRY(tcx_attention_wide(P.qkv, P.b16, h2.on ? 1 : 0, Bt, P.P2, C2, net->heads, h2.ovf, st));
             else if (ragged)
                 TCX_TRY(tcx_attention_ragged(P.qkv, P.b16, h2.on ? 1 : 0, Bt, P.P2, C2, net->heads, h2.ovf, st));
             else if (h2.on) TCX_TRY(tcx_attention_h2(P.qkv, P.b16, Bt, P.P2, C2, net->heads, h2.ovf, st));

@@ -90,6 +90,7 @@ _SIGS = {
     "tcx_upsample2x": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp]),
     "tcx_attention": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
     "tcx_attention_ragged": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp]),
+    "tcx_attention_wide": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp]),
     # f16x3 split path (h2 storage)
     "tcx_pack_conv_weight_h2": (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_fp]),
     "tcx_conv2d_h2": (c_int, [c_fp, c_fp, c_int, c_int, c_int, c_int, c_int, c_int, c_fp, c_fp, c_fp, c_fp, c_fp,
@@ -194,6 +195,10 @@ _SIGS = {
     "tcx_attention_ragged_bwd_workspace": (c_size, [c_int, c_int, c_int, c_int]),
     "tcx_attention_ragged_bwd": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_size,
                                          c_fp]),
+    "tcx_attention_wide_fwd_lse": (c_int, [c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp]),
+    "tcx_attention_wide_bwd_workspace": (c_size, [c_int, c_int, c_int, c_int]),
+    "tcx_attention_wide_bwd": (c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_int, c_int, c_int, c_int, c_fp, c_size,
+                                       c_fp]),
     "tcx_act_fwd": (c_int, [c_fp, c_fp, c_size, c_int, c_fp]),
     "tcx_act_bwd": (c_int, [c_fp, c_fp, c_fp, c_size, c_int, c_fp]),
     "tcx_mse_loss": (c_int, [c_fp, c_fp, c_size, c_fp, c_fp, c_size, c_fp]),

@@ -515,8 +515,9 @@ class Upsample2xFn(torch.autograd.Function):
 # Fused training attention (csrc/attention_bwd.hip): the forward keeps only the row log-sum-exp and the
 # backward recomputes P tile by tile, so no [B, heads, N, N] tensor exists (the GEMM chain below passes
 # four of them through HBM per step).  Token counts outside that pair's set (96x96: N = 576) run its any-N
-# siblings (csrc/attention_ragged.hip, csrc/attention_ragged_bwd.hip).  TCX_ATTN_FUSED=0 keeps the chain for
-# every shape (A/B).
+# siblings (csrc/attention_ragged.hip, csrc/attention_ragged_bwd.hip), and head dims 80 / 96 / 128 (base_ch 160 /
+# 192 / 256) the wide pair (csrc/attention_wide.hip, csrc/attention_wide_bwd.hip) at any token count.
+# TCX_ATTN_FUSED=0 keeps the chain for every shape (A/B).
 _ATTN_FUSED = os.environ.get("TCX_ATTN_FUSED", "1") != "0"
 
 
@@ -532,6 +533,11 @@ def _attn_ragged_ok(N: int, C: int, heads: int) -> bool:
     return _ATTN_FUSED and lib().tcx_attention_ragged_bwd_workspace(1, N, C, heads) > 0
 
 
+def _attn_wide_ok(N: int, C: int, heads: int) -> bool:
+    """any N at head dim 80, 96 or 128: tcx_attention_wide_fwd_lse / tcx_attention_wide_bwd"""
+    return _ATTN_FUSED and lib().tcx_attention_wide_bwd_workspace(1, N, C, heads) > 0
+
+
 class AttentionFn(torch.autograd.Function):
     """SDPA over qkv [B, N, 3C] (q | k | v channel blocks, head h = channels h*d..h*d+d) -> [B, N, C]."""
 
@@ -545,14 +551,18 @@ class AttentionFn(torch.autograd.Function):
         ctx.heads = heads
         ctx.fused = _attn_fused_ok(N, C, heads)
         ctx.ragged = not ctx.fused and _attn_ragged_ok(N, C, heads)
-        if ctx.fused or ctx.ragged:
+        ctx.wide = not ctx.fused and not ctx.ragged and _attn_wide_ok(N, C, heads)
+        if ctx.fused or ctx.ragged or ctx.wide:
             out, lse = _empty((B, N, C), qkv), _empty((B, heads, N), qkv)
             if ctx.fused:
                 check(L.tcx_attention_fwd_lse(ptr(qkv), ptr(out), ptr(lse), B, N, C, heads, _st(qkv)),
                       "tcx_attention_fwd_lse")
-            else:
+            elif ctx.ragged:
                 check(L.tcx_attention_ragged_fwd_lse(ptr(qkv), ptr(out), ptr(lse), B, N, C, heads, _st(qkv)),
                       "tcx_attention_ragged_fwd_lse")
+            else:
+                check(L.tcx_attention_wide_fwd_lse(ptr(qkv), ptr(out), ptr(lse), B, N, C, heads, _st(qkv)),
+                      "tcx_attention_wide_fwd_lse")
             ctx.save_for_backward(qkv, out, lse)
             return out
         scale = 1.0 / math.sqrt(d)
@@ -581,14 +591,15 @@ class AttentionFn(torch.autograd.Function):
             check(L.tcx_attention_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), B, N, C3 // 3, heads,
                                       ptr(ws), ws.numel(), _st(qkv)), "tcx_attention_bwd")
             return dqkv, None
-        if ctx.ragged:
+        if ctx.ragged or ctx.wide:
+            name = "tcx_attention_ragged_bwd" if ctx.ragged else "tcx_attention_wide_bwd"
             qkv, out, lse = ctx.saved_tensors
             B, N, C3 = qkv.shape
-            nb = int(L.tcx_attention_ragged_bwd_workspace(B, N, C3 // 3, heads))
+            nb = int(getattr(L, name + "_workspace")(B, N, C3 // 3, heads))
             ws = _ws(qkv.device, nb)
             dqkv = torch.empty_like(qkv)
-            check(L.tcx_attention_ragged_bwd(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), B, N, C3 // 3, heads,
-                                             ptr(ws), ws.numel(), _st(qkv)), "tcx_attention_ragged_bwd")
+            check(getattr(L, name)(ptr(qkv), ptr(out), ptr(dout), ptr(lse), ptr(dqkv), B, N, C3 // 3, heads,
+                                   ptr(ws), ws.numel(), _st(qkv)), name)
             return dqkv, None
         qkv, P = ctx.saved_tensors
         B, N, C3 = qkv.shape
