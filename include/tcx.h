@@ -297,6 +297,17 @@ int tcx_attention_wide(const float* qkv, void* out, int out_h2, int Bt, int N, i
  * (H/4)*(W/4) is no multiple of 256 (96x96: 576 tokens, 32x32: 64). */
 int tcx_attention_split_ragged(const void* qkv, void* out, int fmt, int Bt, int N, int C, int heads,
                                void* stream);
+/* tcx_attention_split_ragged's interface at the wide head dims 80, 96 and 128 (another: TCX_EUNSUP, the head
+ * dim named), any N >= 1 (k_attention_split_wide, csrc/attention_split_wide.hip: 128-query workgroups, 32-key
+ * tiles in two LDS stages, a peeled and masked last tile).  qkv [Bt,N,3C] and out [Bt,N,C] in one storage
+ * format, fmt as above: 0 h2 records (three f16 MFMAs per product), 1 bf16 records (one bf16 MFMA of the hi
+ * halves, the output with both halves), 2 two-byte bf16.  Both pointers 16-B aligned.  Same Bt / heads bounds,
+ * every refusal before any launch; Bt == 0 returns TCX_OK and writes nothing.  No range flag (a convex
+ * combination of V rows), no atomics: two runs are bit-equal.  The score U-Net evaluator runs its bottleneck
+ * here at precision 2 whenever base_ch / 2 is 80, 96 or 128, at every token count; at precision 1 where
+ * TCX_ATTN_SPLIT_WIDE selects it (tcx_unet.precision below). */
+int tcx_attention_split_wide(const void* qkv, void* out, int fmt, int Bt, int N, int C, int heads,
+                             void* stream);
 
 /* ------------------------------------------------------------------ score U-Net */
 
@@ -336,7 +347,11 @@ typedef struct tcx_unet {
      * 2: N % 256 == 0 on tcx_attention_split_bf16 / _b2, every other N on tcx_attention_split_ragged).  N above
      * 256 and no multiple of 256: precision 0 on fp32 MFMA by tcx_attention_ragged; precision 1 on whichever
      * of tcx_attention_split_ragged (h2 qkv) and tcx_attention_ragged measured faster end to end
-     * (TCX_ATTN_SPLIT_RAGGED = 1 / 0 selects; OPTLOG.md). */
+     * (TCX_ATTN_SPLIT_RAGGED = 1 / 0 selects; OPTLOG.md).  The wide head dims 80, 96 and 128 (base_ch 160 /
+     * 192 / 256 at four heads), every N: precision 0 on tcx_attention_wide; precision 2 on
+     * tcx_attention_split_wide; precision 1 on whichever of tcx_attention_split_wide (h2 qkv) and
+     * tcx_attention_wide(out_h2 = 1) measured faster end to end (TCX_ATTN_SPLIT_WIDE = 1 / 0 selects;
+     * OPTLOG.md). */
     int precision;
     unsigned* h2_ovf;
 } tcx_unet;

@@ -158,6 +158,9 @@ int unet_body(const tcx_unet* net, const Plan& P, const float* x, int B, const f
     // TCX_ATTN_SPLIT_RAGGED=0: f16x3 at a token count above 256 with tails (96x96) keeps fp32 qkv and
     // tcx_attention_ragged instead of h2 qkv and k_attention_split_ragged (A/B; OPTLOG.md round 15)
     static const bool split_ragged_f16 = env_on("TCX_ATTN_SPLIT_RAGGED");
+    // TCX_ATTN_SPLIT_WIDE=0: f16x3 at head dim 80, 96 or 128 keeps fp32 qkv and tcx_attention_wide(out_h2 = 1)
+    // instead of h2 qkv and k_attention_split_wide (A/B; OPTLOG.md round 17)
+    static const bool split_wide_f16 = env_on("TCX_ATTN_SPLIT_WIDE");
     // TCX_ATTN_BLOCK=0: the bottleneck attention as three launches (qkv conv, k_attention_split, proj conv)
     // instead of k_attn_block + proj (bit-identical; A/B measurements and parity tests)
     static const bool attn_block_on = env_on("TCX_ATTN_BLOCK");
@@ -253,12 +256,16 @@ int unet_body(const tcx_unet* net, const Plan& P, const float* x, int B, const f
         // split path with a supported head dim: the qkv conv writes the evaluation's format and the attention
         // runs on f16x3 / bf16 MFMA: N % 256 == 0 on k_attention_split; a token count with tails (96x96: 576,
         // 32x32: 64) on k_attention_split_ragged, at bf16 always (its only attention) and at f16x3 above 256
-        // tokens where split_ragged_f16 says so.  Else fp32 qkv + fp32-MFMA attention
+        // tokens where split_ragged_f16 says so.  Head dim 80, 96 or 128 (base_ch 160 / 192 / 256 at four heads):
+        // k_attention_split_wide at every token count, at bf16 always (its only attention) and at f16x3 where
+        // split_wide_f16 says so.  Else fp32 qkv + fp32-MFMA attention
         const int D = C2 / net->heads;
         const bool tails = P.P2 % 256 != 0;
         const bool split_attn = h2.on && attn_split_on && C2 % net->heads == 0 &&
                                 (D == 16 || D == 32 || D == 48 || D == 64) &&
                                 (!tails || h2.bf || (P.P2 > 256 && split_ragged_f16));
+        const bool wide = C2 % net->heads == 0 && (D == 80 || D == 96 || D == 128);
+        const bool split_wide = h2.on && attn_split_on && wide && (h2.bf || split_wide_f16);
         // f16x3 at N = 256, C2 = 192, 4 heads: the qkv conv runs inside the attention workgroup
         // (attn_block.hip; its output goes to the free qkv buffer, since the heads of an image read b16
         // while others already write), then the proj launch as below
@@ -267,17 +274,17 @@ int unet_body(const tcx_unet* net, const Plan& P, const float* x, int B, const f
             TCX_TRY(tcx_attn_block_h2(P.b16, P.a16, P.qkv, q.wh, q.wscale, q.b, q.cout_pad, pr.wh, pr.wscale, pr.b,
                                       pr.cout_pad, Bt, P.P2, C2, net->heads, h2.ovf, st));
         } else {
-            ConvGn qa = layer(P.b16, C2, H2, W2, P.qkv, split_attn ? 1 : 0);  // 1x1
+            ConvGn qa = layer(P.b16, C2, H2, W2, P.qkv, (split_attn || split_wide) ? 1 : 0);  // 1x1
             qa.pad = 0;
             TCX_TRY(conv_gn(q, st, qa));
-            TCX_REQUIRE(split_attn || !h2.bf,
-                        "tcx_unet: bf16 precision needs the split attention (head dim 16, 32, 48 or 64; TCX_ATTN_SPLIT on); "
-                        "the wide head dims 80, 96 and 128 evaluate at fp32 and f16x3 only");
+            TCX_REQUIRE(split_attn || split_wide || !h2.bf,
+                        "tcx_unet: bf16 precision needs the split attention (head dim 16, 32, 48, 64, 80, 96 or 128; "
+                        "TCX_ATTN_SPLIT on)");
             // a token count neither <= 256 nor a multiple of 256 (96x96: 576): the any-N fp32-MFMA kernel
             const bool ragged = P.P2 > 256 && tails;
-            // head dim 80, 96 or 128 (base_ch 160 / 192 / 256 at four heads): the wide kernel at every token count
-            const bool wide = C2 % net->heads == 0 && (D == 80 || D == 96 || D == 128);
-            if (split_attn && tails)
+            // head dim 80, 96 or 128 off the split route: the fp32-MFMA wide kernel at every token count
+            if (split_wide) TCX_TRY(tcx_attention_split_wide(P.qkv, P.b16, fmt, Bt, P.P2, C2, net->heads, st));
+            else if (split_attn && tails)
                 TCX_TRY(tcx_attention_split_ragged(P.qkv, P.b16, fmt, Bt, P.P2, C2, net->heads, st));
             else if (split_attn) TCX_TRY(attention_split(P.qkv, P.b16, Bt, P.P2, C2, net->heads, fmt, st));
             else if (wide)

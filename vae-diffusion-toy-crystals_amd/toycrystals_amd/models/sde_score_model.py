@@ -242,7 +242,8 @@ class _UNetPack:
         precision; if an f16x3 run raised the range flag, re-run it in fp32 (one host sync).
         "bf16" (config 5's precision) runs wherever the split path does: base_ch % 32 == 0 and a bottleneck
         token count (H/4)*(W/4) % 32 == 0 (96x96 and 32x32 included: tcx_attention_split_ragged serves the
-        counts that are no multiple of 256); elsewhere it warns once and runs fp32."""
+        counts that are no multiple of 256; base_ch 160, 192 and 256, head dim 80, 96 and 128, included:
+        tcx_attention_split_wide); elsewhere it warns once and runs fp32."""
         prec = _lib.conv_precision()
         split = prec in ("f16x3", "bf16") and self.split_ok and ((H // 4) * (W // 4)) % 32 == 0
         bf = split and prec == "bf16"
